@@ -7,12 +7,21 @@ quant.py:97-104) then decode (quant.py:107-112), 3 HIP launches. With N GPUs (to
 GPU) every rank round-trips its own 1 GiB client update concurrently (weak scaling, no collective in the
 data path); value = N GiB / max-over-ranks time per step.
 
-Also reported on the same line:
-* roofline — the dominant kernel's algorithmic bytes / its average launch time, measured with HIP
-  events on the launch stream inside the timed region, against the 8.0 TB/s HBM3E peak; `traffic` is
-  that kernel's HBM bytes per launch from two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) over the same
-  workload, run as child processes after the timed region (N=1; `--pmc off` or a failed pass falls back
-  to the committed profiles/pmc_traffic.json while its kernel-source hash matches);
+A plain run sets up, warms up, times the K steps, writes its outputs if `--dump-outputs DIR` is given and
+prints the line: the headline keys and what the timed region's own HIP events give (kernels_ms, roofline —
+the dominant kernel's algorithmic bytes / its average launch time against the 8.0 TB/s HBM3E peak, `traffic`
+from the committed profiles/pmc_traffic.json while its kernel-source hash matches — and round_trip_roofline).
+`--dump-outputs DIR` writes rank 0's payload, scale and dequantized floats of the last timed step (a fixed
+seeded sample, float32 .npy; dump_outputs); the input is seeded, so two builds compare output for output.
+
+With `--full`, everything else runs after the timed region and is reported on the same line:
+* decode_cold_ms / cold_round_trip / copy_ceiling_GBs — the decode behind an Infinity-Cache flush and
+  torch's own device-to-device copy;
+* roofline.traffic — the dominant kernel's HBM bytes per launch from two rocprofv3 PMC passes (FETCH_SIZE,
+  WRITE_SIZE) over the same workload, run as child processes (N=1; `--pmc off` or a failed pass keeps the
+  committed summary);
+* c3 / c5_int4 / pcie / stoch_c3 / stoch_c2 (N=1, or --extras on) — BASELINE's other single-GPU configs and
+  the host-inclusive rates, each with its parity against the reference's ATen ops;
 * cpu_baseline — the reference's ATen op sequence (quant.py:100-103,110) timed on this host's cores
   (rank 0, N=1), over a bounded sample of the same workload;
 * exchange (N > 1, or --exchange on) — BASELINE configs[3] (C4) on the same buffers after the timed
@@ -21,7 +30,7 @@ Also reported on the same line:
   bucket with per-tensor scales. Both check the gathered rows and the mean across ranks. Never part of
   `value`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 outside torchrun starts N rank processes of this script itself (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* set per child, one free 127.0.0.1 port) before anything touches the GPU, and exits
@@ -59,6 +68,13 @@ def parse():
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--bits", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed headline also run everything else the benchmark measures or checks: the "
+                        "cold decode and copy ceiling, the exchange legs, the extras, the CPU baseline and the live "
+                        "PMC passes (each still governed by its own option below); off: the headline alone")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps write what the last timed step computed (rank 0's payload, scale and "
+                        "dequantized floats; a fixed seeded sample of the two 2^28-element arrays) as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=15.0, help="budget for the CPU baseline sample")
     p.add_argument("--exchange", choices=("auto", "on", "off"), default="auto",
@@ -1019,6 +1035,25 @@ def exchange_bucket_leg(dev, bits: int, world: int, steps: int, warmup: int):
             "GiB_per_s": round(world * int(lay.sizes.sum()) * 4 / GIB / t, 2)}
 
 
+DUMP_EDGE = 4096                      # --dump-outputs: the first and last elements kept whole ...
+DUMP_SAMPLE = 1 << 22                 # ... plus this many seeded positions (2 arrays x 16 MiB in all)
+
+
+def dump_outputs(path: str, q: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files in
+    `path`: payload.npy (the int8 codes) and dequantized.npy, both at the same fixed positions of the flat 2^28
+    elements (the first and last DUMP_EDGE, then DUMP_SAMPLE positions drawn by numpy's PCG64 seeded 0 — the
+    same on every run and build), and scale.npy (the one fp32 scale). int8 is exact in float32."""
+    os.makedirs(path, exist_ok=True)
+    n = q.numel()
+    idx = np.concatenate([np.arange(DUMP_EDGE), np.arange(n - DUMP_EDGE, n),
+                          np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE)]).astype(np.int64)
+    idx_dev = torch.from_numpy(idx).to(q.device)
+    np.save(os.path.join(path, "payload.npy"), q.reshape(-1)[idx_dev].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "dequantized.npy"), out.reshape(-1)[idx_dev].cpu().numpy())
+    np.save(os.path.join(path, "scale.npy"), scale.cpu().numpy())
+
+
 def plumbing_check(args):
     """--plumbing-check: the N-rank path of this script without a GPU (gloo): every rank joins, reports
     itself, spins for (rank + 1) * 50 ms between the two barriers, and rank 0 prints the max over ranks."""
@@ -1101,11 +1136,16 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed, world)
 
-    decode_cold = cold_decode_ms(lib, qp, n, sp, op, stream)
-    copy_ceiling = copy_ceiling_GBs(x, out, stream)
+    if args.dump_outputs and rank == 0:   # before any later leg writes `out` again
+        dump_outputs(args.dump_outputs, q, scale, out)
+
+    decode_cold = copy_ceiling = None
+    if args.full:
+        decode_cold = cold_decode_ms(lib, qp, n, sp, op, stream)
+        copy_ceiling = copy_ceiling_GBs(x, out, stream)
 
     exchange = None
-    if args.exchange == "on" or (args.exchange == "auto" and world > 1):
+    if args.full and (args.exchange == "on" or (args.exchange == "auto" and world > 1)):
         if world == 1:
             import torch.distributed as dist
             dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{free_port()}", rank=0, world_size=1,
@@ -1133,7 +1173,6 @@ def main():
     alg_bytes = KERNEL_BYTES[dominant] * n
     achieved = alg_bytes / (per_kernel[dominant] * 1e-3) / 1e9
     kernels_ms = sum(per_kernel.values())
-    cold_ms = per_kernel["absmax"] + per_kernel["quantize"] + decode_cold
     line = {
         "metric": "GiB/s device-resident quantize+dequantize, 1 GiB fp32 grads, 1/2/4/8 GPU",
         "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1146,22 +1185,25 @@ def main():
                      "traffic": pmc_traffic(dominant), "traffic_source": "profiles/pmc_traffic.json",
                      "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": round(per_kernel[dominant], 4)},
         "kernels_ms": {k: round(v, 4) for k, v in per_kernel.items()},
-        "decode_cold_ms": round(decode_cold, 4),
-        # the receiver-side round trip: a peer decodes a payload that did not just leave its own encode
-        "cold_round_trip": {"kernel_ms": round(cold_ms, 4), "GiB_per_s": round(gib_per_rank / (cold_ms * 1e-3), 2),
-                            "achieved_GBs": round(14 * n / (cold_ms * 1e-3) / 1e9, 1),
-                            "frac": round(14 * n / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "copy_ceiling_GBs": round(copy_ceiling, 1),
         "round_trip_roofline": {"alg_bytes": 14 * n, "kernel_ms": round(kernels_ms, 4),
                                 "achieved_GBs": round(14 * n / (kernels_ms * 1e-3) / 1e9, 1),
                                 "frac": round(14 * n / (kernels_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                 "wall_frac": round(14 * n / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
         "cpu_baseline": None,
     }
+    if args.full:
+        cold_ms = per_kernel["absmax"] + per_kernel["quantize"] + decode_cold
+        line["decode_cold_ms"] = round(decode_cold, 4)
+        # the receiver-side round trip: a peer decodes a payload that did not just leave its own encode
+        line["cold_round_trip"] = {"kernel_ms": round(cold_ms, 4),
+                                   "GiB_per_s": round(gib_per_rank / (cold_ms * 1e-3), 2),
+                                   "achieved_GBs": round(14 * n / (cold_ms * 1e-3) / 1e9, 1),
+                                   "frac": round(14 * n / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+        line["copy_ceiling_GBs"] = round(copy_ceiling, 1)
     if exchange is not None:
         line["exchange"] = exchange
         line["exchange_c3"] = exchange_c3
-    if args.extras == "on" or (args.extras == "auto" and world == 1):
+    if args.full and (args.extras == "on" or (args.extras == "auto" and world == 1)):
         # BASELINE's other single-GPU configs and the host-inclusive rate, after the timed headline (never in
         # `value`); each carries its own parity against the reference's ATen ops
         for key, fn, st in (("c3", extra_c3, 20), ("c5_int4", extra_c5, 10), ("pcie", extra_pcie, 5),
@@ -1171,12 +1213,12 @@ def main():
             except Exception as e:  # noqa: BLE001
                 line[key] = {"error": f"{type(e).__name__}: {e}"[:400]}
             torch.cuda.empty_cache()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu, parity = cpu_baseline(x, args.bits, args.cpu_seconds, q, scale)
         line["cpu_baseline"] = cpu
         line["parity_vs_reference_ops"] = parity
     under_profiler = any(k.startswith("ROCPROF") for k in os.environ)   # rocprofv3 configures its tool via env
-    if world == 1 and args.pmc == "auto" and not under_profiler:
+    if args.full and world == 1 and args.pmc == "auto" and not under_profiler:
         live, note = pmc_live(args.bits)
         if live is not None and live.get(KERNEL_SYMBOLS[dominant]) is not None:
             line["roofline"]["traffic"] = live[KERNEL_SYMBOLS[dominant]]

@@ -1,7 +1,8 @@
 """bench.py's output contract on the GPU (the line the driver parses): exactly one JSON line on stdout with the
 headline keys, n_gpus = 1, a roofline object for the dominant kernel, and value consistent with ms_per_step.
 A short run: 3 timed steps, no CPU baseline, no PMC passes, no exchange leg, no extras (each is covered
-elsewhere)."""
+elsewhere). Everything beyond the headline sits behind --full; the plain run is the headline alone, and
+--dump-outputs writes what its last timed step computed."""
 
 import json
 import os
@@ -16,7 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_emits_one_contract_line():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--pmc", "off", "--exchange", "off", "--extras", "off"],
                        cwd=REPO, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -42,10 +43,54 @@ def test_bench_emits_one_contract_line():
     assert 0.0 < cr["frac"] < 1.0 and cr["GiB_per_s"] > 0
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line holds the headline and what the timed region's own events give, and none of
+    the legs that run after it. --dump-outputs writes float32 arrays, 64 MB at the most, that equal the codec's
+    encode + decode of the same seeded input at the sampled positions (so two runs, or two builds, compare)."""
+    import numpy as np
+    import torch
+
+    import bench
+    from adfl_amd import ops
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")],
+                       cwd=REPO, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "kernels_ms", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["cpu_baseline"] is None
+    assert abs(d["value"] - 1.0 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+    for k in ("decode_cold_ms", "cold_round_trip", "copy_ceiling_GBs", "exchange", "exchange_c3", "c3", "c5_int4",
+              "pcie", "stoch_c3", "stoch_c2", "parity_vs_reference_ops", "traffic_by_kernel"):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["dequantized.npy", "payload.npy", "scale.npy"]
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in files}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in files) <= 64 * 10 ** 6
+    m = 2 * bench.DUMP_EDGE + bench.DUMP_SAMPLE
+    assert got["payload"].shape == got["dequantized"].shape == (m,) and got["scale"].shape == (1,)
+    # the same input (device generator, seed 0 = rank 0) through the codec, at the dump's positions
+    dev = torch.device("cuda", 0)
+    x = torch.randn(bench.SHAPE, device=dev, generator=torch.Generator(device=dev).manual_seed(0)) * 1e-3
+    q, s = ops.encode(x, 8)
+    out = ops.decode(q, s)
+    n = x.numel()
+    idx = np.concatenate([np.arange(bench.DUMP_EDGE), np.arange(n - bench.DUMP_EDGE, n),
+                          np.random.default_rng(0).integers(0, n, size=bench.DUMP_SAMPLE)])
+    idx = torch.from_numpy(idx).to(dev)
+    assert np.array_equal(got["payload"], q.reshape(-1)[idx].float().cpu().numpy())
+    assert np.array_equal(got["dequantized"].view(np.uint32), out.reshape(-1)[idx].cpu().numpy().view(np.uint32))
+    assert np.array_equal(got["scale"].view(np.uint32), s.reshape(1).cpu().numpy().view(np.uint32))
+
+
 def test_bench_exchange_leg_checks_itself():
     """The C4 exchange leg at world 1 over RCCL (--exchange on): after its timed steps it verifies the
     gathered rows against the sent rows and the exact_self=False mean across ranks, and says so."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--pmc", "off", "--exchange", "on", "--extras", "off"],
                        cwd=REPO, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -64,7 +109,7 @@ def test_bench_two_ranks_share_one_gpu():
     """bench.py --gpus 2 end to end on a one-GPU box (hidden --share-gpu: both ranks on cuda:0, gloo): the
     launcher, both ranks' timed round trips, the max over ranks, rank 0's single line with n_gpus 2 and
     value = 2 GiB per step, and the exchange leg (host-staged all-gather) verifying itself across ranks."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--pmc", "off", "--share-gpu"],
                        cwd=REPO, capture_output=True, text=True, timeout=115)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -91,7 +136,7 @@ def test_bench_eight_ranks_share_one_gpu():
     received row's fingerprint equals its sender's, and the exact_self=False mean is identical on all ranks."""
     import time
     t0 = time.perf_counter()
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline", "--pmc", "off", "--share-gpu"],
                        cwd=REPO, capture_output=True, text=True, timeout=230)
     wall = time.perf_counter() - t0
@@ -116,7 +161,7 @@ def test_bench_extras_c3_c5_pcie():
     """The objects bench.py adds after the timed headline at N = 1: C3 (ResNet-18-sized
     bucket, flushed), C5 (4 GiB int4 round trip) and the host-inclusive rates (pinned 1 GiB round trip, the C3
     CPU dict through SLQChannel), each with its parity against the reference's ATen ops true."""
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--pmc", "off", "--exchange", "off", "--extras", "on"],
                        cwd=REPO, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -2,7 +2,7 @@
 bench legs, to tell the leg's own cost from the state earlier legs leave behind:
 
     python tools/host_dict_order.py head            # the leg alone
-    python tools/host_dict_order.py c3+c5+pinned    # after the C3, C5 and pinned 1 GiB legs, as bench.py runs it
+    python tools/host_dict_order.py c3+c5+pinned    # after the C3, C5 and pinned 1 GiB legs, as bench.py --full runs it
 """
 import json, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
