@@ -93,7 +93,11 @@ constexpr int kLane = 16;                         // steps per lane
 constexpr int kSeg = 64 * kLane;                  // 1024 steps: one wave's segment
 constexpr int64_t kShortMax = 1 << 16;            // tensors up to this size skip phases A-C (fp16 / bf16 / fp64)
 #ifndef ADFL_TN_SHORT_MAX_F32
+#ifdef ADFL_TN_WALKER
+#define ADFL_TN_SHORT_MAX_F32 (1 << 16)  // the walker's kWalkMax (torch_norm_walk.h): longer tensors are the phases'
+#else
 #define ADFL_TN_SHORT_MAX_F32 (1 << 19)
+#endif
 #endif
 constexpr int64_t kShortMaxF32 = ADFL_TN_SHORT_MAX_F32;  // fp32: k_tn_short (one block per tensor) up to this size
 template <int DT> constexpr int64_t short_max() {  // fp32 / bf16: k_tn_short(_bf16); fp16: k_tn_short_f16; fp64: D
@@ -1930,14 +1934,23 @@ __global__ __launch_bounds__(256) void k_tn_tfirst(const adfl_slq_chunk* __restr
   if (ch.first_chunk == ci) tfirst[ch.tensor] = (int)ci;
 }
 
+// A tensor that the caller's `kinds` hint did not name (a long one under ADFL_TORCH_NORM_SHORT alone, a short
+// one under ADFL_TORCH_NORM_LONG alone) gets a quiet NaN from the kernel that skips it for its size: the launches
+// that would compute it were not made, and its slot is never left unwritten (include/adfl_stoch.h).
+__device__ __forceinline__ void unnamed_nan(double* __restrict__ norms64, float* __restrict__ norms32, int tensor) {
+  if (norms64) norms64[tensor] = __builtin_nan("");
+  if (norms32) norms32[tensor] = __builtin_nanf("");
+}
+
 // One block per tensor (blockIdx.x = tensor, its first chunk from tfirst) of at most max_n elements (longer
-// ones return). The 8 waves stream the tensor in 8192-element segments: every thread loads 16 consecutive-lane
+// ones return, with a NaN norm if nan_long: no phased launches follow). The 8 waves stream the tensor in
+// 8192-element segments: every thread loads 16 consecutive-lane
 // dwords per segment (buffer loads whose range ends at the chain steps' end, so the rest reads as +0, which no
 // chain notices), two segments ahead in registers, and stages them chain-major into LDS; wave c then reads its
 // lanes' 16-step runs of chain c (4 ds_read_b128 each) and advances the chain by short_segment. Then the lane
 // sum left to right, the n % 8 tail and the sqrt, as k_norm_walk does.
 __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks,
-                                                         const int* __restrict__ tfirst, int64_t max_n,
+                                                         const int* __restrict__ tfirst, int64_t max_n, int nan_long,
                                                          double* __restrict__ norms64, float* __restrict__ norms32) {
   __shared__ __attribute__((aligned(16))) float buf[2 * 8 * kShRow + 4];  // + the spare slot (off[] < 0 elements)
   __shared__ float s_acc[8];
@@ -1949,7 +1962,10 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
   const int ci = tfirst[blockIdx.x];
   const adfl_slq_chunk ch = chunks[ci];
   const int64_t n = (int64_t)(ch.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[ci + ch.nchunks - 1].len;
-  if (n > max_n) return;
+  if (n > max_n) {
+    if (nan_long && threadIdx.x == 0) unnamed_nan(norms64, norms32, ch.tensor);
+    return;
+  }
   const float* xt = x + ch.start;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (n < 8) {
@@ -2154,14 +2170,18 @@ static_assert(kShortMax <= 2 * kGrain, "k_tn_short_f16 holds two pieces per tens
 
 __global__ __launch_bounds__(64 * kH16Waves) void k_tn_short_f16(const uint16_t* __restrict__ x,
                                                                   const adfl_slq_chunk* __restrict__ chunks,
-                                                                  const int* __restrict__ tfirst, int64_t max_n, int threads,
-                                                                  double* __restrict__ norms64, float* __restrict__ norms32) {
+                                                                  const int* __restrict__ tfirst, int64_t max_n, int nan_long,
+                                                                  int threads, double* __restrict__ norms64,
+                                                                  float* __restrict__ norms32) {
   __shared__ __attribute__((aligned(16))) float buf[kH16Waves][kH16Row];
   __shared__ float s_acc[kH16Waves];
   const int ci = tfirst[blockIdx.x];
   const adfl_slq_chunk ch = chunks[ci];
   const int64_t n = (int64_t)(ch.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[ci + ch.nchunks - 1].len;
-  if (n > max_n) return;
+  if (n > max_n) {
+    if (nan_long && threadIdx.x == 0) unnamed_nan(norms64, norms32, ch.tensor);
+    return;
+  }
   const uint16_t* const xt = x + ch.start;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const Split sp = split_of(n, threads);
@@ -2279,14 +2299,17 @@ __device__ __forceinline__ float rn_bf16(float f) {
 // loads in flight while one is walked.
 __global__ __launch_bounds__(kShThreads) void k_tn_short_bf16(const uint16_t* __restrict__ x,
                                                                const adfl_slq_chunk* __restrict__ chunks,
-                                                               const int* __restrict__ tfirst, int64_t max_n,
+                                                               const int* __restrict__ tfirst, int64_t max_n, int nan_long,
                                                                double* __restrict__ norms64, float* __restrict__ norms32) {
   __shared__ __attribute__((aligned(16))) float buf[2][8 * kShRow];
   __shared__ float s_acc[8];
   const int ci = tfirst[blockIdx.x];
   const adfl_slq_chunk ch = chunks[ci];
   const int64_t n = (int64_t)(ch.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[ci + ch.nchunks - 1].len;
-  if (n > max_n) return;
+  if (n > max_n) {
+    if (nan_long && threadIdx.x == 0) unnamed_nan(norms64, norms32, ch.tensor);
+    return;
+  }
   const uint16_t* const xt = x + ch.start;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const auto bf = [](uint32_t h) { return __uint_as_float(h << 16); };
@@ -2405,12 +2428,15 @@ __global__ void k_sh_stats_print() {
 
 // Phase D, one wave per chain: grid (tensors, 8) — by_chunk: (chunks, 8), only tensors' first chunks work
 // (layouts of short tensors only, where phase A, which fills tfirst, did not run); blockIdx.y strides the
-// chains (one chain per CU, so eight chains of one tensor do not share a SIMD). skip_short: fp32 tensors up
-// to kShortMaxF32 are k_tn_short's (ADFL_TN_WALKER builds: the in-order walker's). Each chain's exact accumulator goes to
-// chain_acc[tensor][chain] for k_tn_finish.
+// chains (one chain per CU, so eight chains of one tensor do not share a SIMD). skip: kSkipShort — tensors up
+// to short_max<DT>() are not phase D's (a short kernel's: fp32 k_tn_short, ADFL_TN_WALKER builds the in-order
+// walker, bf16 / fp16 theirs; or `kinds` did not name them); kSkipLong — longer ones are not (`kinds` did not
+// name them: phases A-C did not run); kSkipNan — no other launch writes the skipped ones, so k_tn_finish gives
+// them unnamed_nan. Each chain's exact accumulator goes to chain_acc[tensor][chain] for k_tn_finish.
+enum { kSkipShort = 1, kSkipLong = 2, kSkipNan = 4 };
 template <int DT>
 __global__ __launch_bounds__(64) void k_tn_chains(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks, int64_t nall,
-                                                  const int* __restrict__ tfirst, int by_chunk, int skip_short,
+                                                  const int* __restrict__ tfirst, int by_chunk, int skip,
                                                   int threads, const double* __restrict__ S, const Rec* __restrict__ recs,
                                                   const double4* __restrict__ maps, const int* __restrict__ wing,
                                                   const double4* __restrict__ winmaps, double* __restrict__ chain_acc) {
@@ -2425,7 +2451,7 @@ __global__ __launch_bounds__(64) void k_tn_chains(const void* __restrict__ x, co
   }
   const Tensor T = tensor_of(chunks, ci, nall);
   const bool long_ = T.n > short_max<DT>();
-  if (skip_short && !long_) return;
+  if (skip & (long_ ? kSkipLong : kSkipShort)) return;
   const Split sp = split_of(T.n, threads);
   const int nchains = D::kContig ? (int)sp.nt : D::NC;
 #ifdef ADFL_TN_STATS
@@ -2443,7 +2469,7 @@ __global__ __launch_bounds__(64) void k_tn_chains(const void* __restrict__ x, co
 // The lane sum (strided) or the chain sums in order (fp16), the tail, sqrt, rounding to the dtype.
 template <int DT>
 __global__ __launch_bounds__(64) void k_tn_finish(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks, int64_t nall,
-                                                  const int* __restrict__ tfirst, int by_chunk, int skip_short,
+                                                  const int* __restrict__ tfirst, int by_chunk, int skip,
                                                   int threads, const double* __restrict__ chain_acc,
                                                   double* __restrict__ norms64, float* __restrict__ norms32) {
   using D = Dt<DT>;
@@ -2458,7 +2484,10 @@ __global__ __launch_bounds__(64) void k_tn_finish(const void* __restrict__ x, co
     ci = tfirst[blockIdx.x];
   }
   const Tensor T = tensor_of(chunks, ci, nall);
-  if (skip_short && T.n <= short_max<DT>()) return;
+  if (skip & (T.n > short_max<DT>() ? kSkipLong : kSkipShort)) {
+    if (skip & kSkipNan) unnamed_nan(norms64, norms32, T.tensor);
+    return;
+  }
 #ifdef ADFL_TN_STATS
   if (blockIdx.x == 0) {
     for (int w = 0; w < 8; ++w) {
@@ -2550,7 +2579,12 @@ template <int DT>
 int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const int32_t* tfirst, int64_t ntensors,
            int32_t kinds, int threads, void* scratch, double* n64, float* n32, hipStream_t st) {
   const Scratch s = carve(scratch, nchunks, ntensors);
+#ifdef ADFL_TN_WALKER
+  if (DT == ADFL_DTYPE_F32) kinds = ADFL_TORCH_NORM_SHORT | ADFL_TORCH_NORM_LONG;  // the walker writes no NaN: run both
+#endif
   const bool any_long = (kinds & ADFL_TORCH_NORM_LONG) != 0, any_short = (kinds & ADFL_TORCH_NORM_SHORT) != 0;
+  // A tensor `kinds` does not name gets a NaN from the kernel that skips it (unnamed_nan): no launch is added.
+  const int nan_long = !any_long;
   const bool walk = DT == ADFL_DTYPE_F32;  // fp32 short tensors: k_tn_short (ADFL_TN_WALKER builds: the in-order walker)
   // fp16 short tensors: k_tn_short_f16; bf16 / fp64 ones go straight to phase D (with the long ones, or alone)
   const bool own_short = walk || DT == ADFL_DTYPE_F16 || DT == ADFL_DTYPE_BF16;
@@ -2559,7 +2593,8 @@ int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const i
       k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
       tfirst = s.tfirst;
     }
-    k_tn_short_bf16<<<(unsigned)ntensors, kShThreads, 0, st>>>((const uint16_t*)x, chunks, tfirst, short_max<DT>(), n64, n32);
+    k_tn_short_bf16<<<(unsigned)ntensors, kShThreads, 0, st>>>((const uint16_t*)x, chunks, tfirst, short_max<DT>(), nan_long, n64,
+                                                               n32);
 #ifdef ADFL_TN_STATS
     k_sh_stats_print<<<1, 1, 0, st>>>();
 #endif
@@ -2569,8 +2604,8 @@ int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const i
       k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
       tfirst = s.tfirst;
     }
-    k_tn_short_f16<<<(unsigned)ntensors, 64 * kH16Waves, 0, st>>>((const uint16_t*)x, chunks, tfirst, kShortMax, threads,
-                                                                  n64, n32);
+    k_tn_short_f16<<<(unsigned)ntensors, 64 * kH16Waves, 0, st>>>((const uint16_t*)x, chunks, tfirst, kShortMax, nan_long,
+                                                                  threads, n64, n32);
 #ifdef ADFL_TN_STATS
     k_sh_stats_print<<<1, 1, 0, st>>>();
 #endif
@@ -2583,7 +2618,8 @@ int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const i
       k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
       tfirst = s.tfirst;
     }
-    k_tn_short<<<(unsigned)ntensors, kShThreads, 0, st>>>((const float*)x, chunks, tfirst, kShortMaxF32, n64, n32);
+    k_tn_short<<<(unsigned)ntensors, kShThreads, 0, st>>>((const float*)x, chunks, tfirst, kShortMaxF32, nan_long, n64,
+                                                          n32);
 #ifdef ADFL_TN_STATS
     k_sh_stats_print<<<1, 1, 0, st>>>();
 #endif
@@ -2614,14 +2650,17 @@ int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const i
                                                                      s.winmaps);
     // one wave per chain: 8 strided chains, or fp16's pieces (up to min(threads, 512) of them)
     const unsigned cy = DT == ADFL_DTYPE_F16 ? (unsigned)(threads < 8 ? 8 : (threads > kMaxChains ? kMaxChains : threads)) : 8u;
-    k_tn_chains<DT><<<dim3((unsigned)ntensors, cy), 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 0, own_short, threads, s.S, s.recs,
+    // short tensors: a short kernel's (above), phase D's own (fp64), or not named by `kinds`: NaN
+    const int skip = any_short ? (own_short ? kSkipShort : 0) : (kSkipShort | kSkipNan);
+    k_tn_chains<DT><<<dim3((unsigned)ntensors, cy), 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 0, skip, threads, s.S, s.recs,
                                                                  s.maps, s.wing, s.winmaps, s.chain_acc);
-    k_tn_finish<DT><<<(unsigned)ntensors, 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 0, own_short, threads, s.chain_acc, n64,
-                                                       n32);
+    k_tn_finish<DT><<<(unsigned)ntensors, 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 0, skip, threads, s.chain_acc, n64, n32);
   } else if (!own_short) {
-    k_tn_chains<DT><<<dim3((unsigned)nchunks, 8), 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 1, 0, threads, s.S, s.recs,
+    // fp64, short tensors only: a long one (not named by `kinds`: phases A-C did not run) gets a NaN
+    const int skip = kSkipLong | kSkipNan;
+    k_tn_chains<DT><<<dim3((unsigned)nchunks, 8), 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 1, skip, threads, s.S, s.recs,
                                                                 s.maps, s.wing, s.winmaps, s.chain_acc);
-    k_tn_finish<DT><<<(unsigned)nchunks, 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 1, 0, threads, s.chain_acc, n64, n32);
+    k_tn_finish<DT><<<(unsigned)nchunks, 64, 0, st>>>(x, chunks, nchunks, s.tfirst, 1, skip, threads, s.chain_acc, n64, n32);
   }
   return (int)hipGetLastError();
 }
@@ -2653,6 +2692,7 @@ int adfl_torch_norms_work(int32_t dtype, const void* d_x, const adfl_slq_chunk* 
                           int64_t scratch_bytes, double* d_norms64, float* d_norms32, void* stream) {
   if (nchunks < 0 || ntensors < 0 || (nchunks > 0 && (!d_x || !d_chunks || !d_scratch)) || (!d_norms64 && !d_norms32))
     return ADFL_E_ARG;
+  if (kinds & ~(ADFL_TORCH_NORM_SHORT | ADFL_TORCH_NORM_LONG)) return ADFL_E_ARG;  // before anything is launched
   if (nchunks == 0) return ADFL_OK;
   // threads only shapes fp16's split (at most kMaxChains pieces per tensor); the other dtypes ignore it
   if (ntensors <= 0 || ntensors > nchunks || threads < 1 || (dtype == ADFL_DTYPE_F16 && threads > adfl_tnx::kMaxChains))

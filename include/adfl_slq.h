@@ -28,7 +28,10 @@ extern "C" {
 #endif
 
 /* 2 (round 5): adfl_stoch_norms_torch, adfl_stoch_torch_norm_scratch_bytes and adfl_stoch_torch_norm_walk_max
- * were replaced by adfl_torch_norms (adfl_stoch.h); the absmax / quantize kernels took new arguments. */
+ * were replaced by adfl_torch_norms (adfl_stoch.h); the absmax / quantize kernels took new arguments.
+ * Within 2, adfl_torch_norm_short_max() changed meaning: it is the fp16 / fp64 short-tensor bound only (fp32 /
+ * bf16: 2^19); size adfl_torch_norms' `kinds` by adfl_torch_norm_short_max_dt(dtype). `kinds` values other than
+ * 0..3 are now ADFL_E_ARG, and a tensor that `kinds` does not name gets a NaN norm instead of no write. */
 #define ADFL_SLQ_ABI_VERSION 2
 
 enum {

@@ -70,14 +70,20 @@ enum { ADFL_TORCH_NORM_SHORT = 1, ADFL_TORCH_NORM_LONG = 2 };
  *   kinds:   which tensors the bucket holds, so launches with nothing to do are skipped:
  *            ADFL_TORCH_NORM_SHORT (some of at most adfl_torch_norm_short_max_dt(dtype) elements: fp32, bf16
  *            and fp16 ones in one launch, one block per tensor) | ADFL_TORCH_NORM_LONG (some longer: the phased
- *            path); 0 = both.
+ *            path); 0 = both. Any other bit set: ADFL_E_ARG, nothing launched. It is a hint that cannot drop a
+ *            tensor: one it does not name (a longer one under ADFL_TORCH_NORM_SHORT alone, a short one under
+ *            ADFL_TORCH_NORM_LONG alone, whatever the dtype) gets a quiet NaN in d_norms64 / d_norms32 — the
+ *            launches that would compute it were not made — and every named tensor its norm. A correct hint
+ *            costs no launch more than before (the kernel that skips a tensor for its size writes the NaN).
+ *            Size it by adfl_torch_norm_short_max_dt(dtype), not by adfl_torch_norm_short_max().
  *   outputs: d_norms64[t] = the norm as a double (the dtype's value: exact for every dtype) and / or
  *            d_norms32[t] = (float) of it; either may be NULL, not both.
  * d_scratch: adfl_torch_norm_scratch_bytes(nchunks, ntensors) bytes, 256-byte aligned, no initialisation.
  * Up to nine launches, stream-ordered with no host waits (one for layouts of short fp32 / bf16 / fp16 tensors
  * only). */
 int64_t adfl_torch_norm_scratch_bytes(int64_t nchunks, int64_t ntensors);
-int64_t adfl_torch_norm_short_max(void);          /* fp16 / fp64: 65,536 */
+int64_t adfl_torch_norm_short_max(void);          /* the fp16 / fp64 bound only: 65,536. NOT the fp32 / bf16 one
+                                                     (2^19): use adfl_torch_norm_short_max_dt for `kinds` */
 int64_t adfl_torch_norm_short_max_dt(int32_t dtype); /* the short-tensor bound of a dtype (fp32, bf16: 2^19; fp16,
                                                         fp64: 2^16), or ADFL_E_ARG */
 int adfl_torch_norms(int32_t dtype, const void* d_x, const adfl_slq_chunk* d_chunks, int64_t nchunks,

@@ -67,6 +67,18 @@ def test_reference_norm_short_bounds_per_dtype():
     assert lib.adfl_torch_norm_scratch_bytes(100, 10) > 0 > lib.adfl_torch_norm_scratch_bytes(-1, 1)
 
 
+@pytest.mark.parametrize("kinds", [4, 8, 7, -1])
+def test_reference_norm_rejects_invalid_kinds_without_launching(kinds):
+    """`kinds` is ADFL_TORCH_NORM_SHORT | ADFL_TORCH_NORM_LONG or 0 (include/adfl_stoch.h): any other bit is an
+    argument error before anything is launched, for every dtype and both entries."""
+    lib = _lib.load()
+    need = lib.adfl_torch_norm_scratch_bytes(1, 1)
+    for dtype in (_lib.DTYPE_F32, _lib.DTYPE_BF16, _lib.DTYPE_F16, _lib.DTYPE_F64):
+        assert lib.adfl_torch_norms(dtype, 16, 16, 1, 1, kinds, 1, 256, need, 16, 16, None) == -1
+        assert lib.adfl_torch_norms_work(dtype, 16, 16, 1, 16, 1, kinds, 1, 256, need, 16, 16, None) == -1
+        assert lib.adfl_torch_norms_work(dtype, 16, 16, 1, None, 1, kinds, 1, 256, need, 16, 16, None) == -1
+
+
 @pytest.mark.parametrize("code,frag", [(0, "ok"), (-1, "invalid argument"), (-2, "bits"), (-3, "aligned"),
                                        (-4, "workspace")])
 def test_strerror(code, frag):

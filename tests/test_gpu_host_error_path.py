@@ -16,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from adfl_amd import _torchhost  # noqa: E402
+from adfl_amd.Channel import quant  # noqa: E402
 from adfl_amd.Channel.quant import CNATChannel, QSGDChannel, SLQChannel  # noqa: E402
 
 
@@ -79,6 +80,15 @@ def _same_dict(a, b):
                            b[k].view(-1).view(torch.int32) if b[k].dtype == torch.float32 else b[k]), k
 
 
+def _assert_drained():
+    """quant._drain's guarantee when the exception leaves: nothing is queued or running on the compute stream or
+    the staging copy streams (asked before any synchronize or further GPU call, which would hide queued work)."""
+    st = quant._staging()
+    assert torch.cuda.current_stream().query(), "compute stream still busy after the failed call"
+    assert st.d2h_stream().query(), "D2H stream still busy after the failed call"
+    assert st.h2d_stream().query(), "H2D stream still busy after the failed call"
+
+
 def _encode(ch, params, seed):
     torch.manual_seed(seed)
     c, _ = ch.on_client_send(params)
@@ -94,6 +104,7 @@ def test_encode_after_a_failed_encode_is_clean(make, call):
     want = _payload_bytes(_encode(ch, p2, 7))            # a clean channel's payload of p2
     with _FailOn(call, 3), pytest.raises(_Boom):
         _encode(ch, p1, 5)                                # fails on the second range's outputs
+    _assert_drained()
     got = _payload_bytes(_encode(ch, p2, 7))
     _same_payload(got, want)
     torch.cuda.synchronize()
@@ -106,6 +117,7 @@ def test_decode_after_a_failed_decode_is_clean(make):
     want, _ = ch.on_server_receive(c2)
     with _FailOn("empty_f32_like", 2), pytest.raises(_Boom):
         ch.on_server_receive(c1)                          # fails on the second range's outputs
+    _assert_drained()
     got, _ = ch.on_server_receive(c2)
     _same_dict(got, want)
     torch.cuda.synchronize()

@@ -466,3 +466,20 @@ def test_cnat_multilaunch_zero_tensor_fixup(align):
         ce, cs = so.cnat_quantize(flat[o:o + n], 8, np.float32(nh[t]), u[o:o + n])
         np.testing.assert_array_equal(eh[o:o + n], ce.view(np.uint8))
         np.testing.assert_array_equal(sh[o:o + n], cs)
+
+
+@pytest.mark.parametrize("where", ["host", "device"])
+@pytest.mark.parametrize("cls", [QSGDChannel, CNATChannel], ids=lambda c: c.__name__)
+def test_default_channel_scales_between_the_short_bounds(cls, where):
+    """A dict whose tensors all lie in (2^16, 2^19]: short for fp32's reference-order norm (one block each), long by
+    the fp16 / fp64 bound that adfl_torch_norm_short_max() still reports. Every scale is torch's own norm of its
+    tensor, from host tensors (the range-pipelined path's per-range `kinds`) and from device tensors."""
+    g = torch.Generator().manual_seed(19)
+    # (ndim > 1: the channels pass 1-d tensors through unquantized)
+    params = {f"l{i}.weight": torch.randn(1, n, generator=g) * 1e-3 for i, n in enumerate([70_000, 300_000, 524_288])}
+    want = {k: torch.linalg.vector_norm(v).item() for k, v in params.items()}
+    sent = {k: v.to("cuda:0") for k, v in params.items()} if where == "device" else params
+    qp, _ = cls(8).on_client_send(sent)
+    torch.cuda.synchronize()
+    for k, w in want.items():
+        assert float(qp.params[k].scale) == w, (k, float(qp.params[k].scale), w)
