@@ -25,81 +25,43 @@
 // does too). Only a step that leaves the binade (a "crossing", about log2 of the norm's growth per chain),
 // a non-finite value, or a step of 2^24 ulps or more is not covered: the reference arithmetic (fma) runs it.
 //
-// Phases (long tensors: more than kShortMax elements), one launch each, every block independent:
-//   A  k_tn_sums: per 8192-element chunk and chain (fp16: piece), the fp64 sum S of x^2 (one read of x;
-//      fp32 / bf16 / fp16, k_tn_sums_sampled: of a 1/16 sample, weighted 16 — their phase C totals are exact, so S only
-//      predicts binades and flags nothing);
+// Phases (long tensors: more than short_max<DT>() elements), one launch each, every block independent:
+//   A  per 8192-element chunk and chain (fp16: piece), the fp64 sum S of x^2: fp64, k_tn_sums_f64 (one read of x);
+//      fp32 / bf16 / fp16, k_tn_sums_sampled: of a 1/16 sample, weighted 16 — their phase C totals are exact, so S
+//      only predicts binades and flags nothing;
 //   B  k_tn_winsums + k_tn_grids: per window of 512 tiles the sum of S, then per tile the exclusive prefix P
 //      (earlier windows + a wave scan) predicts the binade of the accumulator at the tile's start:
 //      g = binade(P (1 + 2^-8)) — a prediction only (a miss leaves the tile uncovered, resolved in D);
-//   C  k_tn_maps: per tile, its integer totals on g and g - 1, order-free (k = rint(hi), rint(2 hi)); a
-//      chunk whose squares may hide a tie is listed for k_tn_maps_exact, which stages it chain-major through
-//      LDS and composes each lane's 16 steps as (Ke, Ko) maps in order (second read of x); fp32: k_tn_maps_f32
-//      (exact fp32 increments); bf16 / fp16, whose ties are real: every chunk straight to k_tn_maps_exact;
+//   C  per tile, its integer totals on g and g - 1, order-free: fp64, k_tn_maps_f64 (k = rint(hi), rint(2 hi));
+//      fp32, k_tn_maps_f32 (exact fp32 increments); a chunk whose squares may hide a tie is listed for
+//      k_tn_maps_exact, which stages it chain-major through LDS and composes each lane's 16 steps as (Ke, Ko)
+//      maps in order (second read of x); bf16 / fp16, whose ties are real: every chunk straight to k_tn_maps_exact;
 //   C2 k_tn_windows: per window, the composition of its tiles' maps for the two binades it can start in;
 //   D  k_tn_chains: one wave per chain: windows 64 at a time on the exact accumulator's binade, the first one
-//      not covered tile by tile, the first tile not covered in segments of 1024 steps (lane sums or maps on
-//      G and G + 1, scanned; the lane that crosses runs its steps with fma); then k_tn_finish: the lane sum
-//      (fp16: piece sums in order), the tail, sqrt and the rounding to the dtype. fp32 runs its segments with
-//      k_tn_short's short_segment and its window / tile scans in fp32 by DPP (integer totals below 2^24).
-// Short tensors, one block per tensor in one launch: fp32 up to kShortMaxF32 elements k_tn_short (ADFL_TN_WALKER
-// builds: the in-order walker, torch_norm_walk.h), bf16 up to the same k_tn_short_bf16, fp16 up to kShortMax
-// k_tn_short_f16; short fp64 tensors go straight to D with every tile resolved in detail. DESIGN.md §10.
+//      not covered tile by tile, the first tile not covered in segments of 1024 steps (the lanes' sums or maps
+//      scanned; the lane that crosses runs its steps with fma): fp32 / bf16 / fp16 by k_tn_short's short_segment,
+//      with the window / tile scans in fp32 by DPP (integer totals below 2^24), fp64 by resolve_segment; then
+//      k_tn_finish: the lane sum (fp16: piece sums in order), the tail, sqrt and the rounding to the dtype.
+// Short tensors, one block per tensor in one launch: fp32 up to kShortMaxF32 elements k_tn_short, bf16 up to the
+// same k_tn_short_bf16, fp16 up to kShortMax k_tn_short_f16; short fp64 tensors go straight to D with every tile
+// resolved in detail. DESIGN.md §10.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "adfl_slq.h"
 #include "adfl_stoch.h"
 
-namespace adfl_tn {
-int launch_walk(const float* x, const adfl_slq_chunk* chunks, int64_t nchunks, float* n32, double* n64, hipStream_t st);
-}
-
 namespace adfl_tnx {
-
-#ifdef ADFL_TN_STATS  // tools/ref_norm_prof.py --stats builds: phase D counters per wave, printed per launch
-__device__ unsigned long long g_tn_stats[8][12];  // window descents, tiles in detail, segment rounds, cycles, cycles in
-// detail, cycles waiting for segment loads, cycles in window descents, window scans, exact-path segment rounds,
-// cycles in segments, cycles waiting for a window's records, cycles in window scans up to a tile in detail
-#define TN_STAT(i, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_tn_stats[blockIdx.y & 7][i], (unsigned long long)(v)); } while (0)
-// k_tn_short's counters, summed over its waves: segments, rounds, exact-map rounds, lanes run with fma, G + 1
-// continuations that finished the segment, cycles in short_segment, cycles per wave, (unused), waves, cycles in
-// stage() (its load waits included), cycles in barriers
-__device__ unsigned long long g_sh_stats[11];
-// one block's timeline (tools: stats builds): per wave, up to 48 (event, clock) pairs — 1 stage start, 2 stage
-// end, 3 run start (LDS read issued), 4 segment start (values in registers), 5 run end, 6 barrier end
-__device__ long long g_sh_tl[8][48][2];
-__device__ int g_sh_tln[8];
-#define SH_TL(e) do { if (shn < 48) { if ((threadIdx.x & 63) == 0) { s_tl[threadIdx.x >> 6][shn][0] = (e); \
-  s_tl[threadIdx.x >> 6][shn][1] = clock64(); } ++shn; } } while (0)  // in LDS: no vmcnt waits added
-#define SH_STAT(i, v) do { shs[i] += (unsigned long long)(v); } while (0)  // per wave, added once at the end
-#define SH_ARG , unsigned long long (&shs)[11]
-#define SH_PASS , shs
-#else
-#define TN_STAT(i, v) do { } while (0)
-#define SH_STAT(i, v) do { } while (0)
-#define SH_ARG
-#define SH_PASS
-#define SH_TL(e) do { } while (0)
-#endif
 
 constexpr int kChunk = ADFL_SLQ_CHUNK_ELEMS;      // 8192: a tile is a chunk's steps of one chain
 constexpr int kSlots = 8;                         // records per chunk: one per chain (strided) or piece (fp16)
 constexpr int kLane = 16;                         // steps per lane
 constexpr int kSeg = 64 * kLane;                  // 1024 steps: one wave's segment
-constexpr int64_t kShortMax = 1 << 16;            // tensors up to this size skip phases A-C (fp16 / bf16 / fp64)
-#ifndef ADFL_TN_SHORT_MAX_F32
-#ifdef ADFL_TN_WALKER
-#define ADFL_TN_SHORT_MAX_F32 (1 << 16)  // the walker's kWalkMax (torch_norm_walk.h): longer tensors are the phases'
-#else
-#define ADFL_TN_SHORT_MAX_F32 (1 << 19)
-#endif
-#endif
-constexpr int64_t kShortMaxF32 = ADFL_TN_SHORT_MAX_F32;  // fp32: k_tn_short (one block per tensor) up to this size
+constexpr int64_t kShortMax = 1 << 16;            // tensors up to this size skip phases A-C (fp16 / fp64)
+constexpr int64_t kShortMaxF32 = 1 << 19;         // fp32 / bf16: k_tn_short(_bf16), one block per tensor, up to here
 template <int DT> constexpr int64_t short_max() {  // fp32 / bf16: k_tn_short(_bf16); fp16: k_tn_short_f16; fp64: D
   return DT == ADFL_DTYPE_F32 || DT == ADFL_DTYPE_BF16 ? kShortMaxF32 : kShortMax;
 }
@@ -271,9 +233,10 @@ __device__ __forceinline__ Map lane_map_exact(const E (&v)[kLane], int g) {
   return Map{se, so - 1.0};
 }
 
-// Lane maps on grids g and g + d (d = +1 or -1) in one pass. SQ (bf16 / fp16 inputs): x^2 has at most 22
-// significant bits, so hi = x^2 / u is exact in fp32 and its fraction decides ties: fp32 / int32 arithmetic,
-// no fp64 (a square that underflows is far below 1/2: no tie, increment 0). Otherwise lane_map_exact twice.
+// Lane maps on grids g and g + d (d = +1 or -1; k_tn_maps_exact, the one caller, asks for g - 1) in one pass.
+// SQ (bf16 / fp16 inputs): x^2 has at most 22 significant bits, so hi = x^2 / u is exact in fp32 and its fraction
+// decides ties: fp32 / int32 arithmetic, no fp64 (a square that underflows is far below 1/2: no tie, increment
+// 0). Otherwise lane_map_exact twice.
 __device__ __forceinline__ float pow2f(int k) { return __int_as_float((k + 127) << 23); }  // -126 <= k <= 128
 // 2^k for -149 <= k <= 127, subnormal powers included (half-ulps of low binades: 2^(G-24) down to G = -125)
 __device__ __forceinline__ float pow2fs(int k) { return k >= -126 ? pow2f(k) : __int_as_float(1 << (k + 149)); }
@@ -528,25 +491,25 @@ __device__ __forceinline__ void load_chunk(const View<DT>& v, int tid, u32x4 (&r
   }
 }
 
-// ---- phase A: per chunk and chain (piece), the fp64 sum of x^2; also tfirst[t] = t's first chunk
-template <int DT>
-__global__ __launch_bounds__(256) void k_tn_sums(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks, int64_t nall,
-                                                 int threads, int* __restrict__ tfirst, double* __restrict__ S) {
-  using D = Dt<DT>;
+// ---- phase A, fp64: per chunk and chain, the fp64 sum of x^2; also tfirst[t] = t's first chunk
+// (the signature is the sampled kernel's; `threads` shapes fp16's split only)
+__global__ __launch_bounds__(256) void k_tn_sums_f64(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks,
+                                                     int64_t nall, int threads, int* __restrict__ tfirst,
+                                                     double* __restrict__ S) {
+  constexpr int DT = ADFL_DTYPE_F64;
   using V = View<DT>;
-  constexpr int EPV = V::EPV, NV = V::NV;
+  constexpr int EPV = V::EPV, NV = V::NV, NC = Dt<DT>::NC;  // 2 elements per vector, 4 chains
   __shared__ double s_red[4][8];
   const int ci = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const Tensor T = tensor_of(chunks, ci, nall);
   if (tid == 0 && ci == T.first) tfirst[T.tensor] = ci;
   if (T.n <= short_max<DT>()) return;
-  const Split sp = split_of(T.n, threads);
-  const ChunkGeo G = geo_of<DT>(T, ci, sp);
+  const ChunkGeo G = geo_of<DT>(T, ci, Split{1, T.n});
   if (G.lim <= 0) return;  // a chunk of tail elements only: no tile
   const V v(x, T.base + G.c0e, G.lim);
   u32x4 r[NV];
   load_chunk<DT>(v, tid, r);
-  double acc[EPV], acc1 = 0.0;  // strided: per vector position; fp16: acc[0] / acc1 = piece 0 / 1
+  double acc[EPV];  // per vector position
 #pragma unroll
   for (int p = 0; p < EPV; ++p) acc[p] = 0.0;
 #pragma unroll
@@ -555,56 +518,32 @@ __global__ __launch_bounds__(256) void k_tn_sums(const void* __restrict__ x, con
 #pragma unroll
     for (int p = 0; p < EPV; ++p) {
       const int e = f * EPV + p - v.delta;
-      const double d = (e >= 0 && e < G.lim) ? (double)V::elem(r[i], p) : 0.0;
-      if constexpr (D::kContig) {
-        if (e < G.bnd) acc[0] = __fma_rn(d, d, acc[0]);
-        else acc1 = __fma_rn(d, d, acc1);
-      } else {
-        acc[p] = __fma_rn(d, d, acc[p]);
-      }
+      const double d = (e >= 0 && e < G.lim) ? V::elem(r[i], p) : 0.0;
+      acc[p] = __fma_rn(d, d, acc[p]);
     }
   }
-  if constexpr (D::kContig) {
+  // lanes whose positions map to the same chains: tid % (NC / EPV)
+  constexpr int kCls = NC / EPV;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      acc[0] += __shfl_xor(acc[0], o, 64);
-      acc1 += __shfl_xor(acc1, o, 64);
+  for (int p = 0; p < EPV; ++p)
+#pragma unroll
+    for (int o = kCls; o < 64; o <<= 1) acc[p] += __shfl_xor(acc[p], o, 64);
+  if (lane < kCls) {
+#pragma unroll
+    for (int p = 0; p < EPV; ++p) {
+      const int c = ((lane * EPV + p - v.delta) % NC + NC) % NC;
+      s_red[wave][c] = acc[p];
     }
-    if (lane == 0) {
-      s_red[wave][0] = acc[0];
-      s_red[wave][1] = acc1;
-    }
-    __syncthreads();
-    if (tid < 2 && (tid == 0 || G.bnd < G.len))
-      S[slot_of(ci, tid, T.nall)] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
-  } else {
-    // lanes whose positions map to the same chains: tid % (NC / EPV) (NC / EPV = 2, or 1 for bf16)
-    constexpr int kCls = D::NC / EPV;
-#pragma unroll
-    for (int p = 0; p < EPV; ++p)
-#pragma unroll
-      for (int o = kCls; o < 64; o <<= 1) acc[p] += __shfl_xor(acc[p], o, 64);
-    if (lane < kCls) {
-#pragma unroll
-      for (int p = 0; p < EPV; ++p) {
-        const int c = ((lane * EPV + p - v.delta) % D::NC + D::NC) % D::NC;
-        s_red[wave][c] = acc[p];
-      }
-    }
-    __syncthreads();
-    if (tid < D::NC)
-      S[slot_of(ci, tid, T.nall)] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
   }
+  __syncthreads();
+  if (tid < NC) S[slot_of(ci, tid, T.nall)] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
 }
 
 // fp32 / bf16 phase A: the same sample (16 of a chunk's 256 lines, weighted 16) and tfirst, one wave per chunk and
 // kSumsCPW chunks per wave with every load issued first — a block per chunk issued 2 KB and waited (66 us on C2,
 // latency-bound); lane l loads vectors f0 = 8 (16 (l / 8) + rot) + l % 8 and f0 + 1024 (lines l / 8 and
 // l / 8 + 8 of the sample), so the lanes of one parity hold the same chains and no LDS or barrier is needed.
-#ifndef ADFL_TN_SUMS_CPW
-#define ADFL_TN_SUMS_CPW 2
-#endif
-constexpr int kSumsCPW = ADFL_TN_SUMS_CPW;  // chunks per wave in the sampled phase A
+constexpr int kSumsCPW = 2;  // chunks per wave in the sampled phase A
 // (bf16 — 2-byte elements, 8 to a vector, each vector one element of every chain — takes the same sample: 8 of
 // its chunk's 128 lines, lane l loading vector f0 only, and every lane holding all 8 chains)
 // (fp16: the same 8 lines; a lane's 8 elements are summed into the chunk's two pieces, split at the piece edge)
@@ -787,77 +726,66 @@ __global__ __launch_bounds__(256) void k_tn_grids(const adfl_slq_chunk* __restri
 }
 
 // ---- phase C: per chunk and chain (piece), the totals on the predicted binades g and g - 1
-// Fast path, order-free: with hi = RN(x^2 / u) in the accumulator's type, k = rint(hi) is R(x^2 / u)
-// unless hi - k = +-1/2 (where the exact value decides, and a tie is possible) — and on g - 1, R(2 x^2 / u)
-// = 2 k + rint(2 (hi - k)), exact unless hi - k = +-1/4. A chunk where any lane meets one of those is listed
-// for k_tn_maps_exact: staged chain-major through LDS, each lane's 16 steps composed in order as maps.
-template <int DT>
-__global__ __launch_bounds__(256) void k_tn_maps(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks, int64_t nall,
-                                                 int threads, Rec* __restrict__ recs, double4* __restrict__ maps,
-                                                 int* __restrict__ exact_list) {
-  using D = Dt<DT>;
+// fp64, fast path, order-free: with hi = RN(x^2 / u), k = rint(hi) is R(x^2 / u) unless hi - k = +-1/2 (where
+// the exact value decides, and a tie is possible) — and on g - 1, R(2 x^2 / u) = 2 k + rint(2 (hi - k)), exact
+// unless hi - k = +-1/4. A chunk where any lane meets one of those is listed for k_tn_maps_exact: staged
+// chain-major through LDS, each lane's 16 steps composed in order as maps.
+// (the signature is k_tn_maps_exact's; `threads` shapes fp16's split only)
+__global__ __launch_bounds__(256) void k_tn_maps_f64(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks,
+                                                     int64_t nall, int threads, Rec* __restrict__ recs,
+                                                     double4* __restrict__ maps, int* __restrict__ exact_list) {
+  constexpr int DT = ADFL_DTYPE_F64;
   using V = View<DT>;
-  constexpr bool W = D::kWide;
-  using A_t = typename Acc<W>::T;
-  constexpr int EPV = V::EPV, NV = V::NV;
-  constexpr A_t kM = W ? (A_t)6755399441055744.0 : (A_t)12582912.0f;   // 1.5 * 2^52 / 1.5 * 2^23
-  constexpr A_t kBig = W ? (A_t)0x1p50 : (A_t)0x1p21;                   // hi at or above: rint(2 hi) by kM fails
-  // the largest square (NaN: not covered): fp32 as its bit pattern (squares are >= +0, NaN's pattern is above
-  // +inf's, so an unsigned max propagates it in one instruction); fp64 by value, NaN replaced by +inf
-  using M_t = typename std::conditional<W, double, uint32_t>::type;
-  __shared__ A_t s_k[4][8][2];
-  __shared__ M_t s_mx[4][8];
+  constexpr int EPV = V::EPV, NV = V::NV, NC = Dt<DT>::NC;  // 2 elements per vector, 4 chains
+  constexpr double kBig = 0x1p50;  // hi at or above: rint(2 hi) by kMagic fails
+  __shared__ double s_k[4][8][2];
+  __shared__ double s_mx[4][8];
   __shared__ int s_g[8], s_slow, s_fl[4][8];
   const int ci = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const Tensor T = tensor_of(chunks, ci, nall);
   if (T.n <= short_max<DT>()) return;
-  const Split sp = split_of(T.n, threads);
-  const ChunkGeo G = geo_of<DT>(T, ci, sp);
+  const ChunkGeo G = geo_of<DT>(T, ci, Split{1, T.n});
   if (G.lim <= 0) return;
-  const int npieces = D::kContig ? (G.bnd < G.len ? 2 : 1) : D::NC;
   const V v(x, T.base + G.c0e, G.lim);
   u32x4 r[NV];
   load_chunk<DT>(v, tid, r);  // first: the record load below must not hold the chunk's loads back
-  if (tid < npieces) s_g[tid] = rec_g<W>(recs[slot_of(ci, tid, T.nall)]);
+  if (tid < NC) s_g[tid] = rec_g<true>(recs[slot_of(ci, tid, T.nall)]);
   __syncthreads();
-  // per position (strided) or piece (fp16): scale of x so hi = x^2 / u on g: xs = x 2^(s >> 1), hi = xs xs (2)
-  constexpr int kP = D::kContig ? 2 : EPV;
-  A_t sa[kP], sb[kP];
+  // per position: scale of x so hi = x^2 / u on g: xs = x 2^(s >> 1), hi = xs xs (2)
+  double sa[EPV], sb[EPV];
 #pragma unroll
-  for (int p = 0; p < kP; ++p) {
-    const int c = D::kContig ? (p < npieces ? p : 0) : ((tid * EPV + p - v.delta) % D::NC + D::NC) % D::NC;
-    const int s = Acc<W>::kM - s_g[c];
-    sa[p] = (A_t)pow2(s >> 1);
-    sb[p] = (s & 1) ? (A_t)2 : (A_t)1;
+  for (int p = 0; p < EPV; ++p) {
+    const int c = ((tid * EPV + p - v.delta) % NC + NC) % NC;
+    const int s = Acc<true>::kM - s_g[c];
+    sa[p] = pow2(s >> 1);
+    sb[p] = (s & 1) ? 2.0 : 1.0;
   }
-  // per element: k = rint(hi) and k1 = rint(2 hi) (the totals on g and g - 1), the largest hi, and whether
-  // |hi - k| is 1/2 or 1/4 (a tie on g or g - 1 the rounding of hi may hide: the chunk goes to the exact path)
-  A_t K0[kP], K1[kP];
-  M_t mx[kP];
-  bool fl[kP];
+  // per element: k = rint(hi) and k1 = rint(2 hi) (the totals on g and g - 1), the largest hi (NaN: +inf, not
+  // covered), and whether |hi - k| is 1/2 or 1/4 (a tie on g or g - 1 the rounding of hi may hide: the chunk
+  // goes to the exact path)
+  double K0[EPV], K1[EPV], mx[EPV];
+  bool fl[EPV];
 #pragma unroll
-  for (int p = 0; p < kP; ++p) {
-    K0[p] = K1[p] = (A_t)0;
-    mx[p] = (M_t)0;
+  for (int p = 0; p < EPV; ++p) {
+    K0[p] = K1[p] = mx[p] = 0.0;
     fl[p] = false;
   }
-  const auto step = [&](A_t xv, int q) {
-    const A_t xs = xv * sa[q];
-    const A_t hi = xs * xs * sb[q];
-    const A_t k = (hi + kM) - kM;
-    const A_t rr = hi - k;
-    const A_t ar = __builtin_fabs(rr);
+  const auto step = [&](double xv, int q) {
+    const double xs = xv * sa[q];
+    const double hi = xs * xs * sb[q];
+    const double k = (hi + kMagic) - kMagic;
+    const double rr = hi - k;
+    const double ar = __builtin_fabs(rr);
     K0[q] += k;
-    K1[q] += (hi * (A_t)2 + kM) - kM;
-    if constexpr (W) mx[q] = (hi == hi) ? __builtin_fmax(mx[q], hi) : (M_t)__builtin_inf();
-    else mx[q] = max(mx[q], __float_as_uint(hi));
-    fl[q] |= (ar == (A_t)0.5) | (ar == (A_t)0.25);
+    K1[q] += (hi * 2.0 + kMagic) - kMagic;
+    mx[q] = (hi == hi) ? __builtin_fmax(mx[q], hi) : __builtin_inf();
+    fl[q] |= (ar == 0.5) | (ar == 0.25);
   };
-  if (v.delta == 0 && G.lim == kChunk && G.bnd >= G.len) {  // a whole chunk of one piece: no masks
+  if (v.delta == 0 && G.lim == kChunk) {  // a whole aligned chunk: no masks
 #pragma unroll
     for (int i = 0; i < NV; ++i)
 #pragma unroll
-      for (int p = 0; p < EPV; ++p) step((A_t)V::elem(r[i], p), D::kContig ? 0 : p);
+      for (int p = 0; p < EPV; ++p) step(V::elem(r[i], p), p);
   } else {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -865,85 +793,55 @@ __global__ __launch_bounds__(256) void k_tn_maps(const void* __restrict__ x, con
 #pragma unroll
       for (int p = 0; p < EPV; ++p) {
         const int e = f * EPV + p - v.delta;
-        step((e >= 0 && e < G.lim) ? (A_t)V::elem(r[i], p) : (A_t)0, D::kContig ? (e < G.bnd ? 0 : 1) : p);
+        step((e >= 0 && e < G.lim) ? V::elem(r[i], p) : 0.0, p);
       }
     }
   }
   if (tid == 0) s_slow = 0;
-  const auto mx_max = [](M_t a, M_t b) -> M_t {
-    if constexpr (W) return __builtin_fmax(a, b);
-    else return max(a, b);
-  };
-  if constexpr (D::kContig) {
+  constexpr int kCls = NC / EPV;  // lanes of one class (lane % kCls) hold the same chains
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
+  for (int p = 0; p < EPV; ++p) {
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        K0[p] += __shfl_xor(K0[p], o, 64);
-        K1[p] += __shfl_xor(K1[p], o, 64);
-        mx[p] = mx_max(mx[p], __shfl_xor(mx[p], o, 64));
-      }
-      fl[p] = __ballot(fl[p]) != 0ull;
+    for (int o = kCls; o < 64; o <<= 1) {
+      K0[p] += __shfl_xor(K0[p], o, 64);
+      K1[p] += __shfl_xor(K1[p], o, 64);
+      mx[p] = __builtin_fmax(mx[p], __shfl_xor(mx[p], o, 64));
     }
-    if (lane < 2) {
-      s_k[wave][lane][0] = lane ? K0[1] : K0[0];
-      s_k[wave][lane][1] = lane ? K1[1] : K1[0];
-      s_mx[wave][lane] = lane ? mx[1] : mx[0];
-      s_fl[wave][lane] = lane ? fl[1] : fl[0];
-    }
-  } else {
-    constexpr int kCls = D::NC / EPV;
+    // the flag per class from the wave's ballot
+    const unsigned long long b = __ballot(fl[p]);
+    fl[p] = (b & (0x5555555555555555ull << (lane & 1))) != 0ull;
+  }
+  if (lane < kCls) {
 #pragma unroll
     for (int p = 0; p < EPV; ++p) {
-#pragma unroll
-      for (int o = kCls; o < 64; o <<= 1) {
-        K0[p] += __shfl_xor(K0[p], o, 64);
-        K1[p] += __shfl_xor(K1[p], o, 64);
-        mx[p] = mx_max(mx[p], __shfl_xor(mx[p], o, 64));
-      }
-      // lanes of one class (lane % kCls) hold the same chains: the flag per class from the wave's ballot
-      const unsigned long long b = __ballot(fl[p]);
-      fl[p] = (b & (kCls == 1 ? ~0ull : (0x5555555555555555ull << (lane & 1)))) != 0ull;
-    }
-    if (lane < kCls) {
-#pragma unroll
-      for (int p = 0; p < EPV; ++p) {
-        const int c = ((lane * EPV + p - v.delta) % D::NC + D::NC) % D::NC;
-        s_k[wave][c][0] = K0[p];
-        s_k[wave][c][1] = K1[p];
-        s_mx[wave][c] = mx[p];
-        s_fl[wave][c] = fl[p];
-      }
+      const int c = ((lane * EPV + p - v.delta) % NC + NC) % NC;
+      s_k[wave][c][0] = K0[p];
+      s_k[wave][c][1] = K1[p];
+      s_mx[wave][c] = mx[p];
+      s_fl[wave][c] = fl[p];
     }
   }
   __syncthreads();
-  if (tid < npieces) {
-    A_t k0 = 0, k1 = 0;
-    M_t m = 0;
+  if (tid < NC) {
+    double k0 = 0, k1 = 0, m = 0;
     bool f = false;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
       k0 += s_k[w][tid][0];
       k1 += s_k[w][tid][1];
-      m = mx_max(m, s_mx[w][tid]);
+      m = __builtin_fmax(m, s_mx[w][tid]);
       f |= s_fl[w][tid] != 0;
     }
     const int g = s_g[tid];
-    bool big;
-    if constexpr (W) big = !(m < kBig);
-    else big = m >= __float_as_uint(kBig);
+    const bool big = !(m < kBig);
     const double inf = __builtin_inf();
-    const double e0 = big ? inf : (double)k0;
-    const double e1 = (!big && g - 1 >= Acc<W>::kGmin) ? (double)k1 : inf;
-    // a possible tie matters only where a total can still be covered (below 2^24 / 2^53)
-    if (f && (e0 < Acc<W>::kTop || e1 < Acc<W>::kTop)) s_slow = 1;
+    const double e0 = big ? inf : k0;
+    const double e1 = (!big && g - 1 >= Acc<true>::kGmin) ? k1 : inf;
+    // a possible tie matters only where a total can still be covered (below 2^53)
+    if (f && (e0 < Acc<true>::kTop || e1 < Acc<true>::kTop)) s_slow = 1;
     const int64_t slot = slot_of(ci, tid, T.nall);
-    if constexpr (W) {
-      maps[slot] = make_double4(e0, e0, e1, e1);
-      recs[slot] = make_rec<W>(0.0, 0.0, g, kSide);
-    } else {
-      recs[slot] = make_rec<W>(e0, e1, g, 0u);
-    }
+    maps[slot] = make_double4(e0, e0, e1, e1);
+    recs[slot] = make_rec<true>(0.0, 0.0, g, kSide);
   }
   __syncthreads();
   if (tid == 0 && s_slow) exact_list[atomicAdd(exact_list - 1, 1)] = ci;  // the count sits just before the list
@@ -1297,10 +1195,7 @@ __global__ __launch_bounds__(256) void k_tn_windows(const adfl_slq_chunk* __rest
 // exact map path (lane_map_exact, fp64). Measured against k_norm_walk (the chains run in order) and torch
 // itself: tests/test_gpu_torch_norm.py, test_gpu_torch_norm_dt.py.
 constexpr int kShThreads = 512;                 // wave c runs chain c
-#ifndef ADFL_TN_SHORT_SL
-#define ADFL_TN_SHORT_SL 16
-#endif
-constexpr int kSL = ADFL_TN_SHORT_SL;           // steps per lane's run (a segment: 64 kSL steps of each chain)
+constexpr int kSL = kLane;                      // steps per lane's run (a segment: 64 kSL steps of each chain)
 constexpr int kShSeg = 8 * 64 * kSL;            // elements per segment (16384)
 constexpr int kShLS = kSL + 4;                  // floats per lane's run in LDS (+4: 16-byte reads, no conflicts)
 constexpr int kShRow = 64 * kShLS + 8;          // floats per chain (+8: chains c and c + 4 alone share banks)
@@ -1340,6 +1235,19 @@ __device__ __forceinline__ double lane_d(double v, int l) {  // readlane, so the
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// a lane's run of kSL steps from its 16-byte-aligned LDS row (kSL / 4 ds_read_b128)
+__device__ __forceinline__ void read_run(const float* row, float (&v)[kSL]) {
+  const float4* const rd = reinterpret_cast<const float4*>(row);
+#pragma unroll
+  for (int q = 0; q < kSL / 4; ++q) {
+    const float4 f = rd[q];
+    v[4 * q] = f.x;
+    v[4 * q + 1] = f.y;
+    v[4 * q + 2] = f.z;
+    v[4 * q + 3] = f.w;
+  }
 }
 
 // A lane's 16 steps on binade G (B = 2^G, or +0 for G = -126; h = u / 2): the sum of their increments and whether
@@ -1457,17 +1365,13 @@ __device__ float short_sq_round(const float (&v)[kSL], float acc, int G, int lan
   return lane_fma(w, rebuild<false>((double)(ls > 0 ? lane_f(out, ls - 1) : A), G), lane, ls);
 }
 
-#ifndef ADFL_TN_SERIAL_STEPS
-#define ADFL_TN_SERIAL_STEPS 256
-#endif
-constexpr int kSerial = ADFL_TN_SERIAL_STEPS / ADFL_TN_SHORT_SL;  // lanes (256 steps) run in order at a chain's start (short_segment)
+constexpr int kSerial = 256 / kSL;  // lanes (256 steps) run in order at a chain's start (short_segment)
 
 // One segment of a chain (lane l: steps 16 l .. 16 l + 15, in order) from the exact accumulator acc (wave-uniform).
 // SQ: exact-square inputs (fp16 / bf16), whose tie rounds take short_sq_round instead of the fp64 maps.
 template <bool SQ = false>
-__device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc, int lane SH_ARG) {
+__device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc, int lane) {
   int start = 0;
-  SH_STAT(0, 1);
   if (acc == 0.0f) {
     // A chain's start: the accumulator doubles about every time the step count does (binade crossings at lanes 1,
     // 3, 7, 15, 31, 63), and a crossing round costs about as much as 256 dependent fma: the first kSerial lanes
@@ -1477,7 +1381,6 @@ __device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc,
     start = kSerial;
   }
   while (start < 64) {
-    SH_STAT(1, 1);
     if (!__builtin_isfinite(acc)) {  // inf stays inf unless a NaN follows; NaN stays NaN
       unsigned long long nan = 0ull;
 #pragma unroll
@@ -1493,7 +1396,6 @@ __device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc,
     unsigned long long ties;
     float K0 = lane_incs(v, G, ties);
     if (ties >> start) {  // a possible tie in a lane still to run
-      SH_STAT(2, 1);
       if constexpr (SQ) acc = short_sq_round(v, acc, G, lane, start);
       else acc = short_exact_round(v, acc, G, lane, start);
       continue;
@@ -1504,7 +1406,6 @@ __device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc,
     const unsigned long long ball = __ballot(lane >= start && !(out < top));
     if (ball == 0ull) return lane_f(out, 63);
     const int ls = __builtin_ctzll(ball);
-    SH_STAT(3, 1);
     acc = lane_fma(v, acc + (ls > 0 ? lane_f(I0, ls - 1) : 0.0f), lane, ls);
     start = ls + 1;
     if (start == 64 || !__builtin_isfinite(acc) || grid_of(acc) != G + 1) continue;
@@ -1515,11 +1416,9 @@ __device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc,
     const float I1 = wave_incl_f(lane > ls ? K1 : 0.0f), out1 = acc + I1;
     const unsigned long long b1 = __ballot(lane > ls && !(out1 < pow2f(G + 2)));
     if (b1 == 0ull) {
-      SH_STAT(4, 1);
       return lane_f(out1, 63);
     }
     const int l1 = __builtin_ctzll(b1);
-    SH_STAT(3, 1);
     acc = lane_fma(v, acc + lane_f(I1, l1 - 1), lane, l1);
     start = l1 + 1;
   }
@@ -1527,110 +1426,33 @@ __device__ __forceinline__ float short_segment(const float (&v)[kSL], float acc,
 }
 
 // ---- phase D
-// A segment (<= 1024 steps, lane l holding steps 16 l .. 16 l + 15) run from the exact accumulator acc
-// (fp64 accumulators; fp32 / bf16 / fp16 ones take short_segment, resolve_tile).
-// fp32 accumulators, no tie possible in the wave: each lane's steps add a constant on the binade G and one
-// on G + 1 — both summed in one pass and scanned together, so the usual segment (one crossing) costs one
-// round: the first lane that leaves G runs its steps with fma, and the lanes after it are checked on G + 1
-// from the sums' differences. Otherwise (ties, two crossings, non-finite values) maps, lane by lane.
-template <int DT>
-__device__ __forceinline__ typename Acc<Dt<DT>::kWide>::T resolve_segment(const typename Dt<DT>::E (&v)[kLane],
-                                                                           typename Acc<Dt<DT>::kWide>::T acc, int lane) {
-  constexpr bool W = Dt<DT>::kWide;
-  using A_t = typename Acc<W>::T;
+// A segment (<= 1024 steps, lane l holding steps 16 l .. 16 l + 15) run from the exact accumulator acc, for fp64
+// (fp32 accumulators — fp32 / bf16 / fp16 inputs — take short_segment: resolve_tile). Each round composes the
+// lanes' exact maps on acc's binade G and scans them; the first lane that leaves G runs its steps with fma, and
+// the next round goes on from the lane after it.
+__device__ __forceinline__ double resolve_segment(const double (&v)[kLane], double acc, int lane) {
   int start = 0;
   for (;;) {
     if (!__builtin_isfinite(acc)) {  // inf stays inf unless a NaN follows; NaN stays NaN
       bool nan = false;
 #pragma unroll
       for (int i = 0; i < kLane; ++i) nan |= __builtin_isnan(v[i]);
-      if (__ballot(nan && lane >= start)) acc = (A_t)__builtin_nan("");
+      if (__ballot(nan && lane >= start)) acc = __builtin_nan("");
       return acc;
     }
-    TN_STAT(2, 1);
     const int G = grid_of(acc);
     const double A = a_of(acc);
-    if constexpr (!W && Dt<DT>::kSq) {  // exact-square inputs: the lane maps on G and G + 1 in one pass
-      Map m0, m1;
-      lane_maps_pair<W, true>(v, G, +1, m0, m1);
-      if (lane < start) m0 = Map{0.0, 0.0};
-      const double Al = apply(wave_excl(m0, lane), A);
-      const double out = apply(m0, Al);
-      const unsigned long long ball = __ballot(lane >= start && !(out < Acc<W>::kTop));
-      if (ball == 0ull) return rebuild<W>(__shfl(out, 63, 64), G);
-      const int ls = __builtin_ctzll(ball);
-      A_t a = rebuild<W>(__shfl(Al, ls, 64), G);
-      if (lane == ls) {
-#pragma unroll
-        for (int i = 0; i < kLane; ++i) a = fma_t(v[i], v[i], a);
-      }
-      acc = __shfl(a, ls, 64);
-      start = ls + 1;
-      if (start == 64) return acc;
-      if (__builtin_isfinite(acc) && grid_of(acc) == G + 1) {  // on from lane ls + 1 with the maps on G + 1
-        const Map n1 = lane > ls ? m1 : Map{0.0, 0.0};
-        const double Al1 = apply(wave_excl(n1, lane), a_of(acc));
-        const double out1 = apply(n1, Al1);
-        if (__ballot(lane > ls && !(out1 < Acc<W>::kTop)) == 0ull) return rebuild<W>(__shfl(out1, 63, 64), G + 1);
-      }
-      continue;
-    }
-    if constexpr (!W) {
-      const double sc = pow2(23 - G);
-      double K0 = 0.0, K1 = 0.0;
-      bool maybe = false;
-#pragma unroll
-      for (int i = 0; i < kLane; ++i) {
-        const double d = (double)v[i];
-        const double x2 = d * (d * sc), h = x2 * 0.5, w = x2 * 2.0;
-        K0 += (x2 + kMagic) - kMagic;
-        K1 += (h + kMagic) - kMagic;
-        maybe |= ((w + kMagic) - kMagic) == w && w != 0.0;  // 2v an integer: a tie is possible (on G or G + 1)
-      }
-      if (__ballot(maybe) == 0ull) {
-        if (lane < start) K0 = K1 = 0.0;
-        double I0 = K0, I1 = K1;  // inclusive scans
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const double p0 = __shfl_up(I0, o, 64), p1 = __shfl_up(I1, o, 64);
-          if (lane >= o) {
-            I0 += p0;
-            I1 += p1;
-          }
-        }
-        const double out = A + I0, Al = out - K0;
-        const unsigned long long ball = __ballot(lane >= start && !(out < Acc<W>::kTop));
-        if (ball == 0ull) return rebuild<W>(__shfl(out, 63, 64), G);
-        const int ls = __builtin_ctzll(ball);
-        A_t a = rebuild<W>(__shfl(Al, ls, 64), G);
-        if (lane == ls) {
-#pragma unroll
-          for (int i = 0; i < kLane; ++i) a = fma_t(v[i], v[i], a);
-        }
-        acc = __shfl(a, ls, 64);
-        start = ls + 1;
-        if (start == 64) return acc;
-        // on from lane ls + 1 on G + 1: the K1 sums of lanes ls + 1 .. (exact while the total is below 2^53)
-        if (__builtin_isfinite(acc) && grid_of(acc) == G + 1 && G + 1 <= Acc<W>::kGmax &&
-            __shfl(I1, 63, 64) < 0x1p52) {
-          const double out1 = a_of(acc) + (I1 - __shfl(I1, ls, 64));
-          if (__ballot(lane > ls && !(out1 < Acc<W>::kTop)) == 0ull) return rebuild<W>(__shfl(out1, 63, 64), G + 1);
-        }
-        continue;
-      }
-    }
-    TN_STAT(8, 1);
-    Map m = lane_map_exact<W>(v, G);
+    Map m = lane_map_exact<true>(v, G);
     if (lane < start) m = Map{0.0, 0.0};
     const Map ex = wave_excl(m, lane);
     const double Al = apply(ex, A);
     const double out = apply(m, Al);
-    const bool bad = lane >= start && !(out < Acc<W>::kTop);
+    const bool bad = lane >= start && !(out < Acc<true>::kTop);
     const unsigned long long ball = __ballot(bad);
-    if (ball == 0ull) return rebuild<W>(__shfl(out, 63, 64), G);
+    if (ball == 0ull) return rebuild<true>(__shfl(out, 63, 64), G);
     const int ls = __builtin_ctzll(ball);
     const double As = __shfl(Al, ls, 64);
-    A_t a = rebuild<W>(As, G);
+    double a = rebuild<true>(As, G);
     if (lane == ls) {
 #pragma unroll
       for (int i = 0; i < kLane; ++i) a = fma_t(v[i], v[i], a);
@@ -1656,41 +1478,13 @@ template <int DT>
 __device__ typename Acc<Dt<DT>::kWide>::T resolve_tile(const void* x, const Tensor& T, int c, Split sp, const Tile& tl,
                                                        typename Acc<Dt<DT>::kWide>::T acc, int lane) {
   typename Dt<DT>::E v[kLane];
-  TN_STAT(1, 1);
-#ifdef ADFL_TN_STATS
-  const long long c0 = clock64();
-#endif
   for (int64_t s0 = tl.s0; s0 < tl.s1; s0 += kSeg) {
     load_seg<DT>(x, T, c, sp, s0, s0 + kSeg < tl.s1 ? s0 + kSeg : tl.s1, lane, v);
-#ifdef ADFL_TN_STATS
-    {
-      const long long l0 = clock64();
-      float z = 0.0f;
-#pragma unroll
-      for (int i = 0; i < kLane; ++i) z += (float)v[i];
-      __asm__ volatile("" ::"v"(z));
-      TN_STAT(5, clock64() - l0);
-    }
-#endif
-#ifdef ADFL_TN_STATS
-    const long long r0 = clock64();
-#endif
-    if constexpr (!Dt<DT>::kWide && kSL == kLane) {  // k_tn_short's fp32 rounds (no fp64, DPP scans), same answer;
-                                                      // bf16 / fp16 (exact squares) with their fp32 tie rounds
-#ifdef ADFL_TN_STATS
-      unsigned long long shs[11] = {};
-#endif
-      acc = short_segment<Dt<DT>::kSq>(v, acc, lane SH_PASS);
-    } else {
-      acc = resolve_segment<DT>(v, acc, lane);
-    }
-#ifdef ADFL_TN_STATS
-    TN_STAT(9, clock64() - r0);
-#endif
+    // fp32 accumulators: k_tn_short's rounds (no fp64, DPP scans), bf16 / fp16 (exact squares) with their fp32 tie
+    // rounds; fp64 ones: exact maps
+    if constexpr (!Dt<DT>::kWide) acc = short_segment<Dt<DT>::kSq>(v, acc, lane);
+    else acc = resolve_segment(v, acc, lane);
   }
-#ifdef ADFL_TN_STATS
-  TN_STAT(4, clock64() - c0);
-#endif
   return acc;
 }
 
@@ -1714,16 +1508,6 @@ __device__ typename Acc<Dt<DT>::kWide>::T resolve_window(const void* x, const Te
     mp[k] = maps[slot];
     r[k] = t < nt ? q : Rec{kPad << 24, 0u};
   }
-#ifdef ADFL_TN_STATS
-  {
-    const long long l0 = clock64();
-    uint32_t z = 0;
-#pragma unroll
-    for (int k = 0; k < kTPL; ++k) z ^= r[k].w0 ^ r[k].w1 ^ (uint32_t)__double_as_longlong(mp[k].x);
-    __asm__ volatile("" ::"v"(z));
-    TN_STAT(10, clock64() - l0);
-  }
-#endif
   // the records decoded once per window (every scan re-selects from them by the accumulator's binade): flags,
   // predicted binade, and (fp32) the totals on g and g - 1 as fp32 integers (+inf where not covered)
   uint32_t flk[kTPL];
@@ -1741,10 +1525,6 @@ __device__ typename Acc<Dt<DT>::kWide>::T resolve_window(const void* x, const Te
   int start = 0;  // window tiles before it are done
   const int wlen = nt - w0 < kWinTiles ? (int)(nt - w0) : kWinTiles;
   while (start < wlen) {
-    TN_STAT(7, 1);
-#ifdef ADFL_TN_STATS
-    const long long sc0 = clock64();
-#endif
     if (!__builtin_isfinite(acc)) {  // inf stays inf unless a NaN follows: the remaining tiles' sums say
       bool nan = false;
       for (int64_t u = w0 + start + lane; u < nt; u += 64) {
@@ -1796,7 +1576,6 @@ __device__ typename Acc<Dt<DT>::kWide>::T resolve_window(const void* x, const Te
         }
         const int tb = ls * kTPL + __builtin_amdgcn_readlane(kb, ls);
         acc = rebuild<W>((double)lane_f(Ab, ls), G);
-        TN_STAT(11, clock64() - sc0);
         acc = resolve_tile<DT>(x, T, c, sp, tile_of<DT>(T, c, sp, w0 + tb), acc, lane);
         start = tb + 1;
         continue;
@@ -1832,7 +1611,6 @@ __device__ typename Acc<Dt<DT>::kWide>::T resolve_window(const void* x, const Te
     const int ls = __builtin_ctzll(ball);
     const int tb = ls * kTPL + __shfl(kb, ls, 64);
     acc = rebuild<W>(__shfl(Ab, ls, 64), G);
-    TN_STAT(11, clock64() - sc0);
     acc = resolve_tile<DT>(x, T, c, sp, tile_of<DT>(T, c, sp, w0 + tb), acc, lane);
     start = tb + 1;
   }
@@ -1909,14 +1687,7 @@ __device__ typename Acc<Dt<DT>::kWide>::T resolve_chain(const void* x, const Ten
         ls = __builtin_ctzll(ball);
         acc = rebuild<W>(__shfl(Al, ls, 64), G);
       }
-      TN_STAT(0, 1);
-#ifdef ADFL_TN_STATS
-      const long long w0c = clock64();
-#endif
       acc = resolve_window<DT>(x, T, c, sp, S, recs, maps, (wb + ls) * kWinTiles, nt, acc, lane);
-#ifdef ADFL_TN_STATS
-      TN_STAT(6, clock64() - w0c);
-#endif
       wstart = ls + 1;
     }
   }
@@ -1954,11 +1725,6 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
                                                          double* __restrict__ norms64, float* __restrict__ norms32) {
   __shared__ __attribute__((aligned(16))) float buf[2 * 8 * kShRow + 4];  // + the spare slot (off[] < 0 elements)
   __shared__ float s_acc[8];
-#ifdef ADFL_TN_STATS
-  unsigned long long shs[11] = {};
-  __shared__ long long s_tl[8][48][2];
-  int shn = 0;
-#endif
   const int ci = tfirst[blockIdx.x];
   const adfl_slq_chunk ch = chunks[ci];
   const int64_t n = (int64_t)(ch.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[ci + ch.nchunks - 1].len;
@@ -2021,10 +1787,6 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
   }
   const int nvi = (int)nv;
   const auto stage = [&](const Blk& k, int j) {
-    SH_TL(1);
-#ifdef ADFL_TN_STATS
-    const long long c0 = clock64();
-#endif
     float* const bj = buf + (j & 1) * kBufF;
     const int e0 = j * kShSeg - delta + 4 * tid;                    // this thread's element of vector 0
     const bool last = j * kShSeg - delta + kShSeg + 4 > nvi;         // the block holds the steps' end
@@ -2054,57 +1816,20 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
           bj[(8 - delta + p) * kShRow + 63 * kShLS + kSL - 1] = val;
         }
     }
-#ifdef ADFL_TN_STATS
-    SH_STAT(9, clock64() - c0);
-#endif
-    SH_TL(2);
-  };
-  const auto sync = [&]() {
-#ifdef ADFL_TN_STATS
-    const long long c0 = clock64();
-#endif
-    __syncthreads();
-#ifdef ADFL_TN_STATS
-    SH_STAT(10, clock64() - c0);
-#endif
-    SH_TL(6);
   };
   const int rdo = wave * kShRow + lane * kShLS;
   float acc = 0.0f;
   const auto run = [&](int j) {
-    SH_TL(3);
-    const float4* const rd = reinterpret_cast<const float4*>(buf + (j & 1) * kBufF + rdo);
     float v[kSL];
-#pragma unroll
-    for (int q = 0; q < kSL / 4; ++q) {
-      const float4 f = rd[q];
-      v[4 * q] = f.x;
-      v[4 * q + 1] = f.y;
-      v[4 * q + 2] = f.z;
-      v[4 * q + 3] = f.w;
-    }
-#ifdef ADFL_TN_STATS
-    __asm__ volatile("" ::"v"(v[0]), "v"(v[15]));  // the LDS reads have landed
-    SH_TL(4);
-    const long long r0 = clock64();
-#endif
-    acc = short_segment(v, acc, lane SH_PASS);
-#ifdef ADFL_TN_STATS
-    SH_STAT(5, clock64() - r0);
-    SH_TL(5);
-#endif
+    read_run(buf + (j & 1) * kBufF + rdo, v);
+    acc = short_segment(v, acc, lane);
   };
-#ifdef ADFL_TN_STATS
-  const long long k0 = clock64();
-  SH_STAT(8, 1);
-#endif
   // Two LDS buffers (segment j in buffer j % 2), two register sets: segment j is walked in one buffer, then
   // segment j + 1 staged into the other, while block j + 2 loads; one barrier per segment. Each set is staged in
   // the half after the one that loaded it, after the other set's loads were issued, so the wait before a stage
   // covers its own loads only (vmcnt(5)). (Staged at the loop head, or before the other set's loads, the
   // compiler's merged state at the loop header waited for both sets, and the loads' latency was exposed.)
   Blk ra, rb;
-  SH_TL(0);
   load(ra, 0);
   // every wave's segment-0 loads queue before any segment-1 load (a bare s_barrier: no wait for the loads),
   // so the last wave's first data is not behind the other waves' second segment in the CU's load queue
@@ -2113,7 +1838,7 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
   __builtin_amdgcn_sched_barrier(0);
   load(rb, 1);
   stage(ra, 0);
-  sync();
+  __syncthreads();
   // Each segment's loads in two halves: the first before the walk, the rest after the stage, so the CU's load
   // queue holds at most half a segment more while a wave issues (a whole segment before the walk stalled the
   // issue 0.5-1.4k cycles: queue full; all of it after the stage exposed the latency on long walks). Measured:
@@ -2123,27 +1848,15 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short(const float* __restrict
     run(j);
     stage(rb, j + 1);  // after the walk: its loads have had the walk's time to land (past the end: zeros)
     load_part(ra, j + 2, 2);
-    sync();
+    __syncthreads();
     if (j + 1 >= nseg) break;
     load_part(rb, j + 3, 1);
     run(j + 1);
     stage(ra, j + 2);
     load_part(rb, j + 3, 2);
-    sync();
+    __syncthreads();
     if (j + 2 >= nseg) break;
   }
-#ifdef ADFL_TN_STATS
-  SH_STAT(6, clock64() - k0);
-  if (lane == 0)
-    for (int i = 0; i < 11; ++i) atomicAdd(&g_sh_stats[i], shs[i]);
-  if (blockIdx.x == 7 && lane == 0) {
-    for (int k = 0; k < min(shn, 48); ++k) {
-      g_sh_tl[wave][k][0] = s_tl[wave][k][0];
-      g_sh_tl[wave][k][1] = s_tl[wave][k][1];
-    }
-    g_sh_tln[wave] = min(shn, 48);
-  }
-#endif
   if (lane == 0) s_acc[wave] = acc;
   __syncthreads();
   if (tid == 0) {  // lane sum left to right, the n % 8 tail, sqrt
@@ -2209,9 +1922,6 @@ __global__ __launch_bounds__(64 * kH16Waves) void k_tn_short_f16(const uint16_t*
       k.r2 = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rs, o + 128 * 16, 0, 0));
     };
     float* const row = buf[wave];
-#ifdef ADFL_TN_STATS
-    unsigned long long shs[11] = {};
-#endif
     const auto stage_run = [&](const Blk& k, int j) {
       const int left = (int)(L - (int64_t)j * kSeg < kSeg ? L - (int64_t)j * kSeg : kSeg);  // steps in this segment
       const auto put = [&](const u4& r, int v) {
@@ -2228,21 +1938,10 @@ __global__ __launch_bounds__(64 * kH16Waves) void k_tn_short_f16(const uint16_t*
       put(k.r0, lane);
       put(k.r1, lane + 64);
       if (lane == 0) put(k.r2, 128);
-      const float4* const rd = reinterpret_cast<const float4*>(row + lane * kShLS);
       float v[kSL];
-#pragma unroll
-      for (int q = 0; q < kSL / 4; ++q) {
-        const float4 f = rd[q];
-        v[4 * q] = f.x;
-        v[4 * q + 1] = f.y;
-        v[4 * q + 2] = f.z;
-        v[4 * q + 3] = f.w;
-      }
-      acc = short_segment<true>(v, acc, lane SH_PASS);
+      read_run(row + lane * kShLS, v);
+      acc = short_segment<true>(v, acc, lane);
     };
-#ifdef ADFL_TN_STATS
-    const long long k0c = clock64();
-#endif
     // wave-uniform: four register sets, the next three segments' loads in flight while one is walked (one
     // segment ahead left the HBM latency exposed: two waves per CU have nothing else to hide it behind)
     // (loads past the tensor read zeros from the buffer resource, so they are issued unconditionally: a guarded
@@ -2265,12 +1964,6 @@ __global__ __launch_bounds__(64 * kH16Waves) void k_tn_short_f16(const uint16_t*
       stage_run(k3, j + 3);
       if (j + 4 >= nseg) break;
     }
-#ifdef ADFL_TN_STATS
-    shs[6] += clock64() - k0c;
-    shs[8] += 1;
-    if (lane == 0)
-      for (int i = 0; i < 11; ++i) atomicAdd(&g_sh_stats[i], shs[i]);
-#endif
   }
   if (lane == 0) s_acc[wave] = acc;
   __syncthreads();
@@ -2351,21 +2044,10 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short_bf16(const uint16_t* __
       if (tid == 0) put(k.r2, 2 * kShThreads);
     };
     const int rdo = wave * kShRow + lane * kShLS;
-#ifdef ADFL_TN_STATS
-    unsigned long long shs[11] = {};
-#endif
     const auto run = [&](int j) {
-      const float4* const rd = reinterpret_cast<const float4*>(buf[j & 1] + rdo);
       float v[kSL];
-#pragma unroll
-      for (int q = 0; q < kSL / 4; ++q) {
-        const float4 f = rd[q];
-        v[4 * q] = f.x;
-        v[4 * q + 1] = f.y;
-        v[4 * q + 2] = f.z;
-        v[4 * q + 3] = f.w;
-      }
-      acc = short_segment<true>(v, acc, lane SH_PASS);
+      read_run(buf[j & 1] + rdo, v);
+      acc = short_segment<true>(v, acc, lane);
     };
     Blk ra, rb;
     load(ra, 0);
@@ -2384,11 +2066,6 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short_bf16(const uint16_t* __
       __syncthreads();
       if (j + 2 >= nseg) break;
     }
-#ifdef ADFL_TN_STATS
-    shs[8] += 1;
-    if (lane == 0)
-      for (int i = 0; i < 11; ++i) atomicAdd(&g_sh_stats[i], shs[i]);
-#endif
   }
   if (lane == 0) s_acc[wave] = acc;
   __syncthreads();
@@ -2407,33 +2084,24 @@ __global__ __launch_bounds__(kShThreads) void k_tn_short_bf16(const uint16_t* __
   }
 }
 
-#ifdef ADFL_TN_STATS
-__global__ void k_sh_stats_print() {
-  const unsigned long long* g = g_sh_stats;
-  const double w = g[8] ? (double)g[8] : 1.0;
-  printf("sh_stats waves %llu per wave: segments %.2f rounds %.2f exact-map rounds %.2f fma lanes %.2f g+1 finishes %.2f "
-         "cycles in segments %.0f in stage %.0f in barriers %.0f total %.0f\n", g[8], g[0] / w, g[1] / w, g[2] / w,
-         g[3] / w, g[4] / w, g[5] / w, g[9] / w, g[10] / w, g[6] / w);
-  for (int i = 0; i < 11; ++i) g_sh_stats[i] = 0;
-  const long long t0 = g_sh_tl[0][0][1];
-  for (int w = 0; w < 8; ++w) {
-    printf("sh_tl wave %d:", w);
-    for (int k = 0; k < g_sh_tln[w]; ++k) printf(" %lld@%lld", g_sh_tl[w][k][0], g_sh_tl[w][k][1] - t0);
-    printf("\n");
-    g_sh_tln[w] = 0;
-  }
-}
-#endif
-
-
 // Phase D, one wave per chain: grid (tensors, 8) — by_chunk: (chunks, 8), only tensors' first chunks work
 // (layouts of short tensors only, where phase A, which fills tfirst, did not run); blockIdx.y strides the
 // chains (one chain per CU, so eight chains of one tensor do not share a SIMD). skip: kSkipShort — tensors up
-// to short_max<DT>() are not phase D's (a short kernel's: fp32 k_tn_short, ADFL_TN_WALKER builds the in-order
-// walker, bf16 / fp16 theirs; or `kinds` did not name them); kSkipLong — longer ones are not (`kinds` did not
-// name them: phases A-C did not run); kSkipNan — no other launch writes the skipped ones, so k_tn_finish gives
-// them unnamed_nan. Each chain's exact accumulator goes to chain_acc[tensor][chain] for k_tn_finish.
+// to short_max<DT>() are not phase D's (a short kernel's: fp32 / bf16 / fp16; or `kinds` did not name them);
+// kSkipLong — longer ones are not (`kinds` did not name them: phases A-C did not run); kSkipNan — no other
+// launch writes the skipped ones, so k_tn_finish gives them unnamed_nan. Each chain's exact accumulator goes to
+// chain_acc[tensor][chain] for k_tn_finish.
 enum { kSkipShort = 1, kSkipLong = 2, kSkipNan = 4 };
+// ci = the first chunk of blockIdx.x's tensor; by_chunk: blockIdx.x is a chunk, and only a tensor's first one works
+__device__ __forceinline__ bool block_tensor(const adfl_slq_chunk* chunks, const int* tfirst, int by_chunk, int& ci) {
+  if (by_chunk) {
+    ci = blockIdx.x;
+    if (chunks[ci].first_chunk != ci) return false;
+  } else {
+    ci = tfirst[blockIdx.x];
+  }
+  return true;
+}
 template <int DT>
 __global__ __launch_bounds__(64) void k_tn_chains(const void* __restrict__ x, const adfl_slq_chunk* __restrict__ chunks, int64_t nall,
                                                   const int* __restrict__ tfirst, int by_chunk, int skip,
@@ -2443,27 +2111,16 @@ __global__ __launch_bounds__(64) void k_tn_chains(const void* __restrict__ x, co
   using D = Dt<DT>;
   const int lane = threadIdx.x;
   int ci;
-  if (by_chunk) {
-    ci = blockIdx.x;
-    if (chunks[ci].first_chunk != ci) return;
-  } else {
-    ci = tfirst[blockIdx.x];
-  }
+  if (!block_tensor(chunks, tfirst, by_chunk, ci)) return;
   const Tensor T = tensor_of(chunks, ci, nall);
   const bool long_ = T.n > short_max<DT>();
   if (skip & (long_ ? kSkipLong : kSkipShort)) return;
   const Split sp = split_of(T.n, threads);
   const int nchains = D::kContig ? (int)sp.nt : D::NC;
-#ifdef ADFL_TN_STATS
-  const long long c0 = clock64();
-#endif
   for (int c = blockIdx.y; c < nchains; c += gridDim.y) {
     const double a = (double)resolve_chain<DT>(x, T, c, sp, S, recs, maps, wing, winmaps, long_, lane);
     if (lane == 0) chain_acc[(int64_t)T.tensor * kMaxChains + c] = a;
   }
-#ifdef ADFL_TN_STATS
-  TN_STAT(3, clock64() - c0);
-#endif
 }
 
 // The lane sum (strided) or the chain sums in order (fp16), the tail, sqrt, rounding to the dtype.
@@ -2477,28 +2134,12 @@ __global__ __launch_bounds__(64) void k_tn_finish(const void* __restrict__ x, co
   using A_t = typename Acc<W>::T;
   if (threadIdx.x != 0) return;
   int ci;
-  if (by_chunk) {
-    ci = blockIdx.x;
-    if (chunks[ci].first_chunk != ci) return;
-  } else {
-    ci = tfirst[blockIdx.x];
-  }
+  if (!block_tensor(chunks, tfirst, by_chunk, ci)) return;
   const Tensor T = tensor_of(chunks, ci, nall);
   if (skip & (T.n > short_max<DT>() ? kSkipLong : kSkipShort)) {
     if (skip & kSkipNan) unnamed_nan(norms64, norms32, T.tensor);
     return;
   }
-#ifdef ADFL_TN_STATS
-  if (blockIdx.x == 0) {
-    for (int w = 0; w < 8; ++w) {
-      printf("tn_stats chain %d: windows %llu tiles %llu rounds %llu cycles %llu detail %llu segload %llu windesc %llu"
-             " winscans %llu exactrounds %llu segcycles %llu recwait %llu scancycles %llu\n", w, g_tn_stats[w][0],
-             g_tn_stats[w][1], g_tn_stats[w][2], g_tn_stats[w][3], g_tn_stats[w][4], g_tn_stats[w][5], g_tn_stats[w][6],
-             g_tn_stats[w][7], g_tn_stats[w][8], g_tn_stats[w][9], g_tn_stats[w][10], g_tn_stats[w][11]);
-      for (int i = 0; i < 12; ++i) g_tn_stats[w][i] = 0;
-    }
-  }
-#endif
   const Split sp = split_of(T.n, threads);
   const double* ca = chain_acc + (int64_t)T.tensor * kMaxChains;
   double r;
@@ -2579,58 +2220,32 @@ template <int DT>
 int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const int32_t* tfirst, int64_t ntensors,
            int32_t kinds, int threads, void* scratch, double* n64, float* n32, hipStream_t st) {
   const Scratch s = carve(scratch, nchunks, ntensors);
-#ifdef ADFL_TN_WALKER
-  if (DT == ADFL_DTYPE_F32) kinds = ADFL_TORCH_NORM_SHORT | ADFL_TORCH_NORM_LONG;  // the walker writes no NaN: run both
-#endif
   const bool any_long = (kinds & ADFL_TORCH_NORM_LONG) != 0, any_short = (kinds & ADFL_TORCH_NORM_SHORT) != 0;
   // A tensor `kinds` does not name gets a NaN from the kernel that skips it (unnamed_nan): no launch is added.
   const int nan_long = !any_long;
-  const bool walk = DT == ADFL_DTYPE_F32;  // fp32 short tensors: k_tn_short (ADFL_TN_WALKER builds: the in-order walker)
-  // fp16 short tensors: k_tn_short_f16; bf16 / fp64 ones go straight to phase D (with the long ones, or alone)
-  const bool own_short = walk || DT == ADFL_DTYPE_F16 || DT == ADFL_DTYPE_BF16;
-  if (DT == ADFL_DTYPE_BF16 && any_short) {
-    if (!tfirst) {
-      k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
-      tfirst = s.tfirst;
-    }
-    k_tn_short_bf16<<<(unsigned)ntensors, kShThreads, 0, st>>>((const uint16_t*)x, chunks, tfirst, short_max<DT>(), nan_long, n64,
-                                                               n32);
-#ifdef ADFL_TN_STATS
-    k_sh_stats_print<<<1, 1, 0, st>>>();
-#endif
-  }
-  if (DT == ADFL_DTYPE_F16 && any_short) {
-    if (!tfirst) {
-      k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
-      tfirst = s.tfirst;
-    }
-    k_tn_short_f16<<<(unsigned)ntensors, 64 * kH16Waves, 0, st>>>((const uint16_t*)x, chunks, tfirst, kShortMax, nan_long,
-                                                                  threads, n64, n32);
-#ifdef ADFL_TN_STATS
-    k_sh_stats_print<<<1, 1, 0, st>>>();
-#endif
-  }
-  if (walk && any_short) {
-#ifdef ADFL_TN_WALKER
-    if (int e = adfl_tn::launch_walk((const float*)x, chunks, nchunks, n32, n64, st)) return e;
-#else
+  // fp32 / bf16 / fp16 short tensors: their own kernel; fp64 ones go straight to phase D (with the long ones, or alone)
+  constexpr bool own_short = DT != ADFL_DTYPE_F64;
+  if (own_short && any_short) {
     if (!tfirst) {  // no list from the caller: one launch builds it
       k_tn_tfirst<<<(unsigned)((nchunks + 255) / 256), 256, 0, st>>>(chunks, nchunks, s.tfirst);
       tfirst = s.tfirst;
     }
-    k_tn_short<<<(unsigned)ntensors, kShThreads, 0, st>>>((const float*)x, chunks, tfirst, kShortMaxF32, nan_long, n64,
-                                                          n32);
-#ifdef ADFL_TN_STATS
-    k_sh_stats_print<<<1, 1, 0, st>>>();
-#endif
-#endif
+    if constexpr (DT == ADFL_DTYPE_F32)
+      k_tn_short<<<(unsigned)ntensors, kShThreads, 0, st>>>((const float*)x, chunks, tfirst, short_max<DT>(), nan_long, n64,
+                                                            n32);
+    else if constexpr (DT == ADFL_DTYPE_BF16)
+      k_tn_short_bf16<<<(unsigned)ntensors, kShThreads, 0, st>>>((const uint16_t*)x, chunks, tfirst, short_max<DT>(),
+                                                                 nan_long, n64, n32);
+    else
+      k_tn_short_f16<<<(unsigned)ntensors, 64 * kH16Waves, 0, st>>>((const uint16_t*)x, chunks, tfirst, short_max<DT>(),
+                                                                    nan_long, threads, n64, n32);
   }
   if (any_long) {
     if constexpr (!Dt<DT>::kWide)  // fp32 / bf16 / fp16: a 1/16 sample (S only predicts binades)
       k_tn_sums_sampled<DT><<<(unsigned)((nchunks + 4 * kSumsCPW - 1) / (4 * kSumsCPW)), 256, 0, st>>>(x, chunks, nchunks,
                                                                                                      threads, s.tfirst, s.S);
     else
-      k_tn_sums<DT><<<(unsigned)nchunks, 256, 0, st>>>(x, chunks, nchunks, threads, s.tfirst, s.S);
+      k_tn_sums_f64<<<(unsigned)nchunks, 256, 0, st>>>(x, chunks, nchunks, threads, s.tfirst, s.S);
     k_tn_winsums<DT><<<dim3((unsigned)ntensors, 8, 8), 256, 0, st>>>(chunks, nchunks, s.tfirst, threads, s.S, s.wsum);
     k_tn_grids<DT><<<dim3((unsigned)ntensors, 8, 8), 256, 0, st>>>(chunks, nchunks, s.tfirst, threads, s.S, s.wsum, s.recs);
     if (hipError_t e = hipMemsetAsync(s.exact, 0, 4, st)) return (int)e;
@@ -2642,7 +2257,7 @@ int launch(const void* x, const adfl_slq_chunk* chunks, int64_t nchunks, const i
       k_tn_maps_exact<DT><<<(unsigned)(nchunks < 2048 ? nchunks : 2048), 256, 0, st>>>(x, chunks, nchunks, threads, s.recs,
                                                                                      s.maps, nullptr);
     } else {
-      k_tn_maps<DT><<<(unsigned)nchunks, 256, 0, st>>>(x, chunks, nchunks, threads, s.recs, s.maps, s.exact + 1);
+      k_tn_maps_f64<<<(unsigned)nchunks, 256, 0, st>>>(x, chunks, nchunks, threads, s.recs, s.maps, s.exact + 1);
       k_tn_maps_exact<DT><<<(unsigned)(nchunks < 1024 ? nchunks : 1024), 256, 0, st>>>(x, chunks, nchunks, threads, s.recs,
                                                                                      s.maps, s.exact + 1);
     }

@@ -5,9 +5,9 @@
 // acc[j] = fmaf(x[8i+j], x[8i+j], acc[j]) for i in order, then sums them left to right and runs the n % 8
 // tail (tail_sum: a group of 4 rounded squares, then fmaf); a one-element tensor's norm is |x|
 // (oracle/slq_oracle.c oracle_torch_l2_norm, pinned to torch itself). Each chain is a sequence of
-// dependent roundings: run in order it costs one dependent FMA latency per step. This walker serves the
-// short tensors (<= kWalkMax elements) of adfl_torch_norms (csrc/torch_norm.hip takes the long ones in
-// parallel phases) and ADFL_NORM_L2_TORCH of adfl_stoch_norms_batched.
+// dependent roundings: run in order it costs one dependent FMA latency per step. This walker serves
+// ADFL_NORM_L2_TORCH of adfl_stoch_norms_batched, tensors of any length; adfl_torch_norms (csrc/torch_norm.hip)
+// gives the same bits in parallel phases, and its tests hold the two against each other.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,9 +34,7 @@ __device__ __forceinline__ float tail_sum(const float* x, int64_t d, int64_t n, 
   return b;
 }
 
-constexpr int64_t kWalkMax = 1 << 16;                     // tensors up to this size are walked (k_norm_walk)
-
-// One block per tensor of at most kWalkMax elements (the phased kernels take the longer ones) runs the
+// One block per tensor (blockIdx.x = chunk; only a tensor's first chunk works) runs the
 // 8 chains in order — the reference's loop itself. Its four waves stream the tensor in 2048-element blocks
 // into LDS buffers, chain-major (buf[c][step]), so lane c < 8 of wave 0 reads its chain back 4 steps
 // per ds_read_b128, eight reads ahead of the dependent FMAs (about 6.6 cycles per step,
@@ -44,30 +42,24 @@ constexpr int64_t kWalkMax = 1 << 16;                     // tensors up to this 
 // register ring (2 KiB in flight) took 56 us on C3; with cross-lane shuffles instead of the LDS
 // transpose 95 us, and with its loads under branches (an s_waitcnt vmcnt(0) after each) 312 us.
 constexpr int kWalkThreads = 256;
-#ifndef ADFL_TN_WALK_REGS
-#define ADFL_TN_WALK_REGS 8
-#endif
-constexpr int kWalkRegs = ADFL_TN_WALK_REGS;
+constexpr int kWalkRegs = 8;                          // dwords per thread per block
 constexpr int kWalkBlock = kWalkThreads * kWalkRegs;  // 2048 elements: 256 steps of each chain
 constexpr int kWalkBlockStride = kWalkBlock / 8 + 4;   // floats per chain row (+4: banks, 16-byte reads)
 
 __global__ __launch_bounds__(kWalkThreads) void k_norm_walk(const float* __restrict__ x,
                                                            const adfl_slq_chunk* __restrict__ chunks,
-                                                           int64_t max_n, float* __restrict__ norms,
-                                                           double* __restrict__ norms64 = nullptr) {
+                                                           float* __restrict__ norms) {
   __shared__ __attribute__((aligned(16))) float buf[3][8 * kWalkBlockStride];
   const adfl_slq_chunk ch = chunks[blockIdx.x];
   if ((int64_t)blockIdx.x != ch.first_chunk) return;
   const int64_t n = (int64_t)(ch.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[blockIdx.x + ch.nchunks - 1].len;
-  if (n > max_n) return;
   const float* xt = x + ch.start;
   const int tid = threadIdx.x, c = tid & 7, s0 = tid >> 3;
   if (n < 8) {
     if (tid == 0) {
       const float b = tail_sum(xt, 0, n, 0.0f);
       const float r = n == 1 ? __builtin_fabsf(xt[0]) : (float)__builtin_sqrt((double)b);  // one element: |x|
-      if (norms) norms[ch.tensor] = r;
-      if (norms64) norms64[ch.tensor] = r;
+      norms[ch.tensor] = r;
     }
     return;
   }
@@ -144,8 +136,7 @@ __global__ __launch_bounds__(kWalkThreads) void k_norm_walk(const float* __restr
     if (tid == 0) {
       b = tail_sum(xt, nv, n, b);
       const float r = (float)__builtin_sqrt((double)b);  // correctly rounded fp32 sqrt
-      if (norms) norms[ch.tensor] = r;
-      if (norms64) norms64[ch.tensor] = r;
+      norms[ch.tensor] = r;
     }
   }
 }

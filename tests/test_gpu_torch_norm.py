@@ -1,13 +1,14 @@
-"""GPU: the fp32 reference-order L2 norm (stoch.torch_norms -> adfl_torch_norms: csrc/torch_norm.hip for long
-tensors, the in-order walker csrc/torch_norm_walk.h for short ones), torch's fp32 vector_norm order.
+"""GPU: the fp32 reference-order L2 norm (stoch.torch_norms -> adfl_torch_norms, csrc/torch_norm.hip: k_tn_short
+for short tensors, the phased kernels for long ones), torch's fp32 vector_norm order.
 
 The norm must equal the reference's — torch 2.10's CPU vector_norm, restated in the oracle
 (oracle_torch_l2_norm, pinned to every golden norm by tests/test_stoch_golden.py) — bit for bit, on data
 that exercises every branch of the phased kernels: binade crossings (every tensor's first tiles), ties
 (integer and short-mantissa data, where R(p/u) lands on a half), misses of the grid predictor (a chain
 whose values jump in scale), subnormal and overflowing squares, NaN and inf, empty tiles and the n % 8
-tail, tensors below 8 elements. Also against the sequential one-wave kernel
-(norms_batched NORM_L2_TORCH), across repeated launches and two layouts alternating.
+tail, tensors below 8 elements. Also against the in-order walker
+(norms_batched NORM_L2_TORCH: k_norm_walk, csrc/torch_norm_walk.h), across repeated launches and two layouts
+alternating.
 """
 
 import numpy as np

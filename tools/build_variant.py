@@ -1,7 +1,7 @@
 """Build an A/B variant of libadfl_slq.so with extra -D flags into tools/_variants/ (git-ignored); select it
 at run time with ADFL_LIB_VARIANT=<path> (adfl_amd/_lib.py).
 
-    python tools/build_variant.py stats -DADFL_TN_STATS
+    python tools/build_variant.py philox10 -DADFL_PHILOX_ROUNDS=10
 """
 import os
 import subprocess
