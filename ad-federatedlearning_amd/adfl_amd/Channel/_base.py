@@ -1,0 +1,276 @@
+"""What the SLQ channels (quant.py) and the stochastic channels (stoch.py) share above the staging layer:
+``_CodecChannel``, the class skeleton of a bi-directional codec channel (the reference's six-method surface,
+``receive_add_`` and ``receive_mean`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
+uni-directional variants; and the host aggregate of the entries no device kernel takes (``_aggregate_entries``,
+``device_mean_order_ok``).
+
+An instance holds only what its constructor was given (``bits``; the stochastic channels add ``levels``): it
+is pickled into every Ray actor. Device state lives in the staging layer's per-process cache.
+"""
+
+import time
+from typing import Dict, List, Tuple
+
+import numpy as np
+import torch
+
+from .. import _torchhost, sum_order
+from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters, get_parameter_info
+from .channel import Channel, IdentityChannel
+
+
+def _simple_aggregate(values: List[torch.Tensor]) -> torch.Tensor:
+    """One entry of simple_aggregate (Src/ADFL/model.py:221-234), as the reference computes it."""
+    with torch.no_grad():
+        return torch.sum(torch.stack(values, dim=0), dim=0) / len(values)
+
+
+def device_mean_order_ok() -> bool:
+    """The device mean kernels follow torch's CPU sum(dim=0) order as ATen's AVX2 kernel takes it
+    (csrc/torch_sum_order.h). If this process's torch sums in another order (sum_order.self_check fails:
+    another torch build or CPU kernel), receive_mean decodes and aggregates every entry on the host the
+    reference's way instead, so the device and host halves of one aggregate never disagree; warned once."""
+    ok = sum_order.self_check()
+    if not ok and not _ORDER_WARNED[0]:
+        _ORDER_WARNED[0] = True
+        import warnings
+        warnings.warn("adfl_amd: this torch's CPU sum order differs from the one the device mean kernels "
+                      "restate; receive_mean aggregates on the host (bit-identical, slower)", RuntimeWarning)
+    return ok
+
+
+_ORDER_WARNED = [False]
+
+
+def _aggregate_entries(names: List[str], parts: List[Parameters]) -> Dict[str, torch.Tensor]:
+    """simple_aggregate over the entries `names` of the K dicts `parts` (host tensors: biases, running
+    statistics, counters), with the per-entry call's values but not its per-entry dispatch cost (256
+    biases: about 3 ms of stack / sum / div). Entries of one dtype are concatenated into K rows and summed
+    together: int64 with K elementwise adds (integer sums are exact in any order), fp32 in torch's own CPU
+    summation order (adfl_amd.sum_order: each entry's columns in the order its own
+    torch.sum(torch.stack(...), 0) takes, bit for bit; checked against torch once per process,
+    sum_order.self_check). Then one division and a split into owned tensors. One-element fp32 entries at
+    K >= 8 (torch's inner-sum kernel) and everything else go through simple_aggregate per entry."""
+    k = len(parts)
+    res: Dict[str, torch.Tensor] = {}
+    f32_ok = sum_order.self_check()
+    lists = [[p[n] for n in names] for p in parts]
+    if names and all(isinstance(v, torch.Tensor) for row in lists for v in row):
+        # the classification, the K rows and the owned results in native calls (adfl_torchhost)
+        th = _torchhost.get()
+        uni, code, numel = (a.numpy() for a in th.entry_meta_k(lists))
+        f32 = uni & (code == 0) & f32_ok & (numel > 0) & ~((numel == 1) & (k >= 8))
+        with torch.no_grad():
+            for sel, is_f32 in ((f32, True), (uni & (code == 1), False)):
+                idx = np.nonzero(sel)[0]
+                if idx.size < 2:
+                    continue
+                rows = th.concat_rows(lists, torch.from_numpy(idx))
+                if is_f32:
+                    acc = sum_order.sum_rows(rows, numel[idx].tolist())
+                else:   # int64: K elementwise adds from zero (exact in any order)
+                    acc = torch.zeros_like(rows[0])
+                    for r in rows.unbind(0):
+                        acc = acc + r
+                agg = acc / k
+                for i, t in zip(idx.tolist(), th.split_owned(agg, [lists[0][i] for i in idx.tolist()])):
+                    res[names[i]] = t
+        for n in names:
+            if n not in res:
+                res[n] = _simple_aggregate([p[n] for p in parts])
+        return res
+    groups: Dict[torch.dtype, List[str]] = {}
+    for n in names:
+        vals = [p[n] for p in parts]
+        t0 = vals[0]
+        if not all(isinstance(v, torch.Tensor) and not v.is_cuda and v.is_contiguous() and v.dtype == t0.dtype
+                   and v.shape == t0.shape for v in vals):
+            continue
+        if t0.dtype == torch.int64 or (t0.dtype == torch.float32 and f32_ok and t0.numel() > 0
+                                       and not (t0.numel() == 1 and k >= 8)):
+            groups.setdefault(t0.dtype, []).append(n)
+    with torch.no_grad():
+        for dt, ns in groups.items():
+            if len(ns) < 2:
+                continue
+            sizes = [parts[0][n].numel() for n in ns]
+            if dt == torch.int64:
+                rows = [torch.cat([p[n].reshape(-1) for n in ns]) for p in parts]
+                acc = torch.zeros_like(rows[0])
+                for r in rows:
+                    acc = acc + r
+            else:
+                stacked = torch.stack([torch.cat([p[n].reshape(-1) for n in ns]) for p in parts])
+                acc = sum_order.sum_rows(stacked, sizes)
+            agg = acc / k
+            for n, piece in zip(ns, torch.split(agg, sizes)):
+                shape = parts[0][n].shape
+                res[n] = (piece if piece.shape == shape else piece.view(shape)).clone()
+    for n in names:
+        if n not in res:
+            res[n] = _simple_aggregate([p[n] for p in parts])
+    return res
+
+
+def _passthrough_idle(entries, made: Dict[str, QuantParameter], size: List[int], bits: int, scale, signs, *tail):
+    """_quantize_params' idle(): each call turns up to `batch` of the passthrough `entries` (name, tensor) into
+    payload objects in `made` (the tensor itself as data, `scale`, the shared unused `signs`, `tail`: the
+    fields after q_dtype), counts their bytes in size[0], and returns True while entries are left. The
+    pipelined host encodes call it between staging ranges."""
+    rest = iter(entries)
+    qp = QuantParameter
+
+    def idle(batch=32):
+        for _ in range(batch):
+            e = next(rest, None)
+            if e is None:
+                return False
+            t = e[1]
+            made[e[0]] = qp(t, bits, scale, signs, t.shape, t.dtype, t.dtype, *tail)
+            size[0] += t.nbytes
+        return True
+    return idle
+
+
+class _CodecChannel(Channel):
+    """A bi-directional codec channel; ``receive_add_`` and ``receive_mean`` are written once around the
+    codec's part, which a subclass supplies:
+
+    * ``_quantize_params(params, bits)`` -> QuantParameters, ``_receive(c_params)`` -> (Parameters, seconds);
+    * ``_add_fused(c_params, targets)``: the entries receive_add_ decodes and adds on the device, and
+      ``_decode_add(c_params, names, targets)``, which does it;
+    * ``_mean_host_updates(all_c_params, names)``: receive_mean's common case (K CPU updates of one model)
+      classified in a few native calls -> (fused names, their means, the passthrough names or None), or None
+      when the updates are anything else (they are then classified entry by entry, with the hooks below);
+    * ``_fusable(p)``: an entry the decode-mean launch takes; ``_mean_shape(p)``: its decoded shape (one shape
+      across the updates fuses); ``_mean_payloads(all_c_params, names)``: the means of such entries;
+    * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor."""
+
+    SIGN_BITS = 0    # sent per weight beside its `bits` (the stochastic codecs' sign plane: 1)
+    NORM_BYTES = 4   # sent per quantized tensor: its scale or norm (RQSGD: norm + minimum factor, 8)
+
+    def __init__(self, bits: int) -> None:
+        self.bits = bits
+
+    def on_server_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
+        return self._send(params)
+
+    def on_server_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
+        return self._receive(c_params)
+
+    def on_client_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
+        return self._send(params)
+
+    def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
+        return self._receive(c_params)
+
+    def to_json(self) -> Dict:
+        return {"name": self.__class__.__name__, "bits": self.bits}
+
+    def simulate_bandwidth(self, params: Parameters, mbps: float) -> float:
+        """self.bits (+ SIGN_BITS) for weights, 32 bits for biases, NORM_BYTES per quantized tensor
+        (quant.py:47-58,173-184,313-324,459-470)."""
+        p_info = get_parameter_info(params)
+        num_bytes = p_info.num_non_bias_w * (self.bits + self.SIGN_BITS) / 8
+        num_bytes += p_info.num_bias_w * 4
+        num_bytes += p_info.num_non_bias_t * self.NORM_BYTES
+        transfer_time = num_bytes / (mbps * 1_000_000 / 8)
+        time.sleep(transfer_time)
+        return transfer_time
+
+    def _send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
+        s_time = time.perf_counter()
+        q_params = self._quantize_params(params, self.bits)
+        return q_params, time.perf_counter() - s_time
+
+    def receive_add_(self, c_params: CompressedParameters, targets: List[Parameters]) -> float:
+        """``on_client_receive(c_params)`` followed by ``add_parameters_inpace(t, decoded, 1, 1, False)`` for
+        every ``t`` in ``targets`` — the client pool's ``add_to_model`` / ``add_to_model_all``
+        (Src/ADFL/Client/pool.py:62-75) and QAFeL's hidden-state update (Src/ADFL/Server/qafel.py:176-179),
+        bit-identical to them. Returns the seconds spent.
+
+        The entries ``_add_fused`` names are decoded once on the device and added into every model there
+        (``_decode_add``: no decoded tensor crosses PCIe). Everything else takes the reference's route:
+        decode, then ``mul_(1).add_(decoded, alpha=1)``."""
+        assert isinstance(c_params, QuantParameters)
+        for t in targets:
+            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
+        s_time = time.perf_counter()
+        fused = self._add_fused(c_params, targets)
+        if fused:
+            self._decode_add(c_params, fused, targets)
+        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in fused}, 0)
+        if rest.params:
+            decoded, _ = self.on_client_receive(rest)
+            with torch.no_grad():
+                for t in targets:
+                    for n, d in decoded.items():
+                        t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
+        return time.perf_counter() - s_time
+
+    def receive_mean(self, all_c_params: List[CompressedParameters]) -> Tuple[Parameters, float]:
+        """``simple_aggregate([self.on_server_receive(c)[0] for c in all_c_params])`` — a synchronous
+        server decoding K client updates and averaging them (Src/ADFL/Strategy/simple.py:83-89 over
+        Src/ADFL/model.py:221-234; the peer mean of Examples/ray_ad.py:188). Returns (aggregate, seconds).
+
+        Entries encoded in every update (``_fusable``, one shape) are decoded and averaged on the device in
+        one launch: the K payloads are read once and no decoded copy is materialised. Their mean is summed in
+        torch's CPU order for ``torch.sum(torch.stack(...), dim=0)`` (csrc/torch_sum_order.h: per tensor, a
+        16-row cascade over the SEQ columns, four interleaved partials over each tensor's last n % 32
+        elements), then / K correctly rounded: bit-identical to simple_aggregate on CPU tensors (as the
+        reference runs it, model.py:195-197) for every K (tests/golden/aggregate.npz: the reference executed
+        at K = 1 .. 64; the stochastic codecs' own payloads at K = 5, 8, 16, 20). Everything else (biases,
+        running statistics, empty or non-quantized payloads) is decoded and aggregated as the reference does,
+        on the host, in the same order."""
+        if not all_c_params:
+            raise AssertionError("receive_mean: no updates")   # simple_aggregate asserts len > 0
+        for c in all_c_params:
+            assert isinstance(c, QuantParameters)
+        s_time = time.perf_counter()
+        names = list(all_c_params[0].params.keys())
+        order_ok = device_mean_order_ok()
+        out: Parameters = {}
+        fast = self._mean_host_updates(all_c_params, names) if order_ok else None
+        plain = None
+        if fast is not None:   # every update a CPU dict of the same entries: classified in native calls
+            fused, decoded, plain = fast
+            out.update(zip(fused, decoded))
+        else:
+            fused = [n for n in names if all(n in c.params and self._fusable(c.params[n]) for c in all_c_params)
+                     and len({tuple(self._mean_shape(c.params[n])) for c in all_c_params}) == 1] if order_ok else []
+            if fused:
+                out.update(zip(fused, self._mean_payloads(all_c_params, fused)))
+        rest = [n for n in names if n not in out]
+        if rest:
+            # passthrough entries decode to their own payload tensor (quant.py:111-112): used as they are
+            # (the values _receive hands back, without its per-entry work); the rest through _receive
+            if plain is None:
+                plain = [n for n in rest if all(self._passthrough(c.params[n]) for c in all_c_params)]
+            skip = set(plain)
+            other = [n for n in rest if n not in skip]
+            parts = []
+            for c in all_c_params:
+                part = {n: c.params[n].data for n in plain}
+                if other:
+                    part.update(self._receive(QuantParameters({n: c.params[n] for n in other}, 0))[0])
+                parts.append(part)
+            out.update(_aggregate_entries(rest, parts))
+        return {n: out[n] for n in names}, time.perf_counter() - s_time
+
+    @staticmethod
+    def _mean_shape(p: QuantParameter):
+        return p.shape
+
+    def _passthrough(self, p: QuantParameter) -> bool:
+        return False
+
+
+class _Unidirectional:
+    """Only client -> server is compressed; server -> client and the client's receive use the identity
+    channel (quant.py:115-137,255-277,401-423,548-570)."""
+
+    def on_server_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
+        return IdentityChannel(no_compute_time=True).on_server_send(params)
+
+    def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
+        return IdentityChannel(no_compute_time=True).on_client_receive(c_params)

@@ -31,6 +31,10 @@ way. There is no CPU fallback: without the HIP library these raise.
 fp16 / bf16 / fp64 tensors are encoded as the reference encodes them, in their own dtype's arithmetic (each
 op rounded to the dtype; uniforms on torch.rand's grid for the dtype): one bucket per dtype through the
 *_dt kernels (csrc/stoch_dtype.hip). Their payloads decode like fp32 ones (the reference decodes to fp32).
+
+This module is the stochastic codecs' side of a call: which kernels run over the bucket and how the level and
+sign planes and norms become payloads. How the bucket gets to the device and the results back into owned
+tensors is _staging.py's; the class skeleton shared with the SLQ channels (quant.py) is _base.py's.
 """
 
 import ctypes
@@ -44,11 +48,11 @@ import torch
 from .. import _lib, _torchhost, hostcopy, ops
 from .. import stoch as sops
 from .._lib import check
-from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters, get_parameter_info
-from .channel import Channel, IdentityChannel
-from . import quant as _quant
-from .quant import (_PendingD2H, _aggregate_entries, _chunk_meta, _drain, _hand_out, _host_heap, _ph,
-                    _range_copies, _ranges, _serialized, _stage_in, _stage_rows, _staging, device_mean_order_ok)
+from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
+from . import _staging as _stg
+from ._base import _CodecChannel, _passthrough_idle, _Unidirectional
+from ._staging import (_PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _ph, _range_copies, _ranges,
+                       _rows_from_ptrs, _serialized, _stage_in, _stage_rows, _staging)
 
 _CODECS = ("qsgd", "rqsgd", "cnat")
 
@@ -122,7 +126,7 @@ def _encode_stoch(params: Parameters, names: List[str], codec: str, bits: int, u
     lay = st.layout(tuple(numel.tolist()))
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-    if host_ok and _quant._PIPELINE:
+    if host_ok and _stg._PIPELINE:
         return _encode_stoch_host(tensors, names, hptrs.numpy().view(np.uint64), lay, st, codec, bits, uniforms,
                                   seed, torch_norm, emit or (lambda k, d, g: None), idle or (lambda: False))
     x_dev = _stage_in(tensors, lay, st, "x", torch.float32, host_ptrs=hptrs.numpy().view(np.uint64) if host_ok else None)
@@ -168,19 +172,34 @@ def _encode_stoch(params: Parameters, names: List[str], codec: str, bits: int, u
         pend_lv.finish([t.view(torch.uint8) for t in lv_parts])
         pend_sg.finish(sg_parts)
         return _payloads(names, lv_parts, sg_parts, nm, lay.ntensors, codec)
+
+    def norms_list():
+        torch.cuda.current_stream(dev).synchronize()
+        return nm_host.tolist()
+    datas, signs, nm = _hand_out_planes(lv, sg, lay, tensors, on_cpu, st, norms_list, native_like=True)
+    return _payloads(names, datas, signs, nm, lay.ntensors, codec)
+
+
+def _hand_out_planes(lv, sg, lay, tensors: List[torch.Tensor], on_cpu: List[bool], st, norms_list,
+                     native_like: bool = False):
+    """A device or mixed dict's level and sign planes as owned per-tensor tensors on their inputs' devices:
+    (datas, signs, norms). norms_list() is called once the planes' D2H (when any input is on the CPU) is
+    enqueued: it waits for the stream and returns the norms as a list, so the planes have landed as well.
+    native_like: a device dict of fp32 tensors on the staging's device gets its outputs from one native call."""
+    dev = st.device
+    shapes = [t.shape for t in tensors]
     if any(on_cpu):
         lv_h = st.buf("s_levels_host", lay.total, torch.uint8, pinned=True).view(lv.dtype)
         sg_h = st.buf("s_signs_host", lay.total, torch.int8, pinned=True)
         lv_h.copy_(lv, non_blocking=True)
         sg_h.copy_(sg, non_blocking=True)
-    torch.cuda.current_stream(dev).synchronize()
-    nm = nm_host.tolist()
-    sizes, shapes = lay.sizes.tolist(), [t.shape for t in tensors]
+    nm = norms_list()
+    sizes = lay.sizes.tolist()
     split = lambda buf: [p[:n] for p, n in zip(torch.split(buf, lay.padded.tolist()), sizes)]  # noqa: E731
     lv_parts = _owned_host(lv_h, lay.offsets, shapes) if any(on_cpu) else None
     sg_parts = _owned_host(sg_h, lay.offsets, shapes) if any(on_cpu) else None
     if not any(on_cpu):   # device dict: one scatter launch per plane
-        same = _torchhost.get().device_ptrs(tensors, dev.index, 4)[0]   # all on the staging's device
+        same = native_like and _torchhost.get().device_ptrs(tensors, dev.index, 4)[0]   # all on the staging's device
         lv_dev = _owned_dev(lv, lay, shapes, like=tensors if same else None)
         sg_dev = _owned_dev(sg, lay, shapes, like=tensors if same else None)
     else:
@@ -188,7 +207,7 @@ def _encode_stoch(params: Parameters, names: List[str], codec: str, bits: int, u
         sg_dev = _owned(split(sg), shapes) if not all(on_cpu) else None
     datas = [(lv_parts if cpu else lv_dev)[i] for i, cpu in enumerate(on_cpu)]
     signs = [(sg_parts if cpu else sg_dev)[i] for i, cpu in enumerate(on_cpu)]
-    return _payloads(names, datas, signs, nm, lay.ntensors, codec)
+    return datas, signs, nm
 
 
 def _codec_encode(codec: str, x_dev, lay, bits: int, uniforms, seed: int, levels, signs, norms, mins, ws,
@@ -387,7 +406,6 @@ def _encode_stoch_dt(params: Parameters, names: List[str], codec: str, bits: int
     that dtype's arithmetic (adfl_stoch_encode_batched_dt). Same return as _encode_stoch; the norms are the
     dtype's values as Python floats (norm.item() of the reference's 0-dim norm tensor)."""
     st = _staging()
-    dev = st.device
     tensors = [params[n] for n in names]
     dtype = tensors[0].dtype
     tag = str(dtype).replace("torch.", "")
@@ -407,26 +425,10 @@ def _encode_stoch_dt(params: Parameters, names: List[str], codec: str, bits: int
     else:
         lv, sg, norms, mins = sops.encode_batched_dt(codec, x_dev, lay, bits, uniforms=u, seed=seed,
                                                      counter=COUNTER_BASE[dtype], levels=levels, signs=signs, ws=ws)
-    nm = torch.cat([norms, mins]) if mins is not None else norms
-    on_cpu = [not t.is_cuda for t in tensors]
-    shapes = [t.shape for t in tensors]
-    if any(on_cpu):
-        lv_h = st.buf("s_levels_host", lay.total, torch.uint8, pinned=True).view(lv.dtype)
-        sg_h = st.buf("s_signs_host", lay.total, torch.int8, pinned=True)
-        lv_h.copy_(lv, non_blocking=True)
-        sg_h.copy_(sg, non_blocking=True)
-    nm = nm.cpu().tolist()   # synchronises: the planes' D2H has landed too
-    sizes = lay.sizes.tolist()
-    split = lambda buf: [p[:n] for p, n in zip(torch.split(buf, lay.padded.tolist()), sizes)]  # noqa: E731
-    lv_parts = _owned_host(lv_h, lay.offsets, shapes) if any(on_cpu) else None
-    sg_parts = _owned_host(sg_h, lay.offsets, shapes) if any(on_cpu) else None
-    if not any(on_cpu):   # device dict: one scatter launch per plane
-        lv_dev, sg_dev = _owned_dev(lv, lay, shapes), _owned_dev(sg, lay, shapes)
-    else:
-        lv_dev = _owned(split(lv), shapes) if not all(on_cpu) else None
-        sg_dev = _owned(split(sg), shapes) if not all(on_cpu) else None
-    datas = [(lv_parts if cpu else lv_dev)[i] for i, cpu in enumerate(on_cpu)]
-    signs = [(sg_parts if cpu else sg_dev)[i] for i, cpu in enumerate(on_cpu)]
+    nm_dev = torch.cat([norms, mins]) if mins is not None else norms
+    # .cpu() synchronises: the planes' D2H has landed too
+    datas, signs, nm = _hand_out_planes(lv, sg, lay, tensors, [not t.is_cuda for t in tensors], st,
+                                        lambda: nm_dev.cpu().tolist())
     return _payloads(names, datas, signs, nm, lay.ntensors, codec, dtype)
 
 
@@ -450,7 +452,7 @@ def _payloads(names, datas, signs, nm, ntensors: int, codec: str, dtype: torch.d
 def _decode_stoch(items: List[Tuple[str, QuantParameter]], codec: str, bits: int) -> Dict[str, torch.Tensor]:
     """Decode (levels, signs, norm[, min]) payloads of ndim > 1 tensors in one bucketed pass."""
     st = _staging()
-    if _quant._PIPELINE:
+    if _stg._PIPELINE:
         th = _torchhost.get()
         datas = [p.data for _, p in items]
         signs = [p.signs for _, p in items]
@@ -469,6 +471,13 @@ def _decode_stoch(items: List[Tuple[str, QuantParameter]], codec: str, bits: int
 
 
 _CODEC_ID = {"qsgd": 0, "rqsgd": 1, "cnat": 2}   # ADFL_CODEC_* (include/adfl_stoch.h)
+
+
+def _scales_dev(items: List[Tuple[str, QuantParameter]], codec: str, dev: torch.device) -> torch.Tensor:
+    """The payloads' norms as one fp32 device tensor, RQSGD's minimum factors appended behind them."""
+    return torch.tensor([float(p.scale) for _, p in items] + ([float(p.scale_2) for _, p in items]
+                                                              if codec == "rqsgd" else []),
+                        dtype=torch.float32).to(dev, non_blocking=True)
 
 
 def _decode_stoch_host(st, items, datas, numel: torch.Tensor, lptrs: np.ndarray, sptrs: np.ndarray, codec: str,
@@ -492,9 +501,7 @@ def _decode_stoch_host(st, items, datas, numel: torch.Tensor, lptrs: np.ndarray,
     out_dev = st.buf("d_out", lay.total, torch.float32)
     out_host = st.buf("d_out_host", lay.total, torch.float32, pinned=True)
     ntens = len(items)
-    sc = torch.tensor([float(p.scale) for _, p in items] + ([float(p.scale_2) for _, p in items]
-                                                            if codec == "rqsgd" else []), dtype=torch.float32)
-    s_dev = sc.to(dev, non_blocking=True)
+    s_dev = _scales_dev(items, codec, dev)
     nd = s_dev.data_ptr()
     md = nd + 4 * ntens if codec == "rqsgd" else 0
     chunks_ptr = lay.device_chunks(dev).data_ptr()
@@ -580,10 +587,8 @@ def _decode_stoch_bucket(st, items: List[Tuple[str, QuantParameter]], codec: str
     lay = st.layout(tuple(int(p.data.numel()) for _, p in items))
     lv_dev = _stage_in([p.data.view(torch.uint8) for _, p in items], lay, st, "d_levels", torch.uint8)
     sg_dev = _stage_in([p.signs.view(torch.int8) for _, p in items], lay, st, "d_signs", torch.int8)
-    scales = [float(p.scale) for _, p in items]
     ntens = len(items)
-    sc = torch.tensor(scales + ([float(p.scale_2) for _, p in items] if codec == "rqsgd" else []),
-                      dtype=torch.float32).to(dev, non_blocking=True)
+    sc = _scales_dev(items, codec, dev)
     out_dev = st.buf("d_out", lay.total, torch.float32)
     if codec == "qsgd":
         sops.qsgd_decode_batched(lv_dev, sg_dev, sc[:ntens], lay, bits, out=out_dev)
@@ -621,71 +626,39 @@ def _decode_mean_stoch_host(like: List[torch.Tensor], numel: torch.Tensor, lv_pt
                             sg_ptrs: List[np.ndarray], norms: torch.Tensor, mins, codec: str,
                             bits: int) -> List[torch.Tensor]:
     """_decode_mean_stoch for K CPU updates already checked (_StochChannel._mean_host_updates): both planes of
-    every client gathered straight from the storages into pinned rows (one native gather per client and
-    plane, each row's H2D enqueued as soon as it is staged), one decode-mean launch, the fp32 means handed
-    back as owned CPU tensors shaped like `like`, created by one native call per staging range."""
+    every client gathered straight from the storages into pinned rows (_rows_from_ptrs, once per plane), one
+    decode-mean launch, the fp32 means handed back as owned CPU tensors shaped like `like`, created by one
+    native call per staging range."""
     st = _staging()
     dev = st.device
     lay = st.layout(tuple(numel.tolist()))
     _host_heap(lay)
-    k = len(lv_ptrs)
-    row = (lay.total + 15) // 16 * 16
-    rows = {}
-    for key, ptrs, dt in (("sm_levels", lv_ptrs, torch.uint8), ("sm_signs", sg_ptrs, torch.int8)):
-        d = st.buf(key, k * row, torch.uint8).view(k, row)
-        h = st.buf(key + "_host", k * row, torch.uint8, pinned=True).view(k, row)
-        for r in range(k):
-            hostcopy.copy_pieces(*_range_copies(ptrs[r], lay, h[r].data_ptr(), 1, 0, lay.total, to_bucket=True))
-            d[r].copy_(h[r], non_blocking=True)
-        rows[key] = d if dt == torch.uint8 else d.view(torch.int8)
+    lv_rows = _rows_from_ptrs(lv_ptrs, lay, st, "sm_levels")
+    sg_rows = _rows_from_ptrs(sg_ptrs, lay, st, "sm_signs").view(torch.int8)
     nd = norms.to(dev, non_blocking=True)
     md = mins.to(dev, non_blocking=True) if mins is not None else None
-    out_dev = sops.dequantize_mean_batched(codec, rows["sm_levels"], rows["sm_signs"], nd, lay, bits, mins=md,
+    out_dev = sops.dequantize_mean_batched(codec, lv_rows, sg_rows, nd, lay, bits, mins=md,
                                            out=st.buf("sm_out", lay.total, torch.float32))
     return _hand_out(out_dev, lay, [None] * len(like), [True] * len(like), st, "sm_out", like=like)
 
 
-class _StochChannel(Channel):
-    """Shared body of the three bi-directional stochastic channels."""
+class _StochChannel(_CodecChannel):
+    """Shared body of the three bi-directional stochastic channels: ``simulate_bandwidth`` counts self.bits + 1
+    for weights and signs, 32 bits for biases, the norms (quant.py:173-184,313-324,459-470).
+
+    ``receive_add_``: encoded tensors whose targets are all fp32 tensors on the current device are decoded
+    once, into device memory, and added into every model there. ``receive_mean``: entries encoded in every
+    update are decoded and averaged by one launch (each client's level and sign planes read once); empty
+    tensors take the host route with the biases."""
 
     CODEC = "qsgd"
-    NORM_BYTES = 4  # per quantized tensor: the norm (RQSGD: norm + minimum factor)
+    SIGN_BITS = 1
 
     def __init__(self, bits: int) -> None:
         """The reference's constructor (quant.py:145-147): the L2 norm is the reference's own (see the module
         docstring; ADFL_STOCH_NORM=fp64 selects the correctly rounded one instead)."""
-        self.bits = bits
+        super().__init__(bits)
         self.levels = 2 ** bits - 1
-
-    def on_server_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
-        return self._send(params)
-
-    def on_server_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
-        return self._receive(c_params)
-
-    def on_client_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
-        return self._send(params)
-
-    def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
-        return self._receive(c_params)
-
-    def to_json(self) -> Dict:
-        return {"name": self.__class__.__name__, "bits": self.bits}
-
-    def simulate_bandwidth(self, params: Parameters, mbps: float) -> float:
-        """self.bits + 1 for weights and signs, 32 bits for biases, norms (quant.py:173-184,313-324,459-470)."""
-        p_info = get_parameter_info(params)
-        num_bytes = p_info.num_non_bias_w * (self.bits + 1) / 8
-        num_bytes += p_info.num_bias_w * 4
-        num_bytes += p_info.num_non_bias_t * self.NORM_BYTES
-        transfer_time = num_bytes / (mbps * 1_000_000 / 8)
-        time.sleep(transfer_time)
-        return transfer_time
-
-    def _send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
-        s_time = time.perf_counter()
-        q_params = self._quantize_params(params, self.bits)
-        return q_params, time.perf_counter() - s_time
 
     def _receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
         assert isinstance(c_params, QuantParameters)
@@ -708,76 +681,33 @@ class _StochChannel(Channel):
             vals[i] = t  # passthrough: q_param.data.data
         return dict(zip(names, vals)), time.perf_counter() - s_time
 
-    def receive_mean(self, all_c_params: List[CompressedParameters]) -> Tuple[Parameters, float]:
-        """``simple_aggregate([self.on_server_receive(c)[0] for c in all_c_params])`` — a synchronous server
-        decoding K client updates and averaging them (Src/ADFL/Strategy/simple.py:83-89 over
-        Src/ADFL/model.py:221-234). Returns (aggregate, seconds).
-
-        Entries encoded in every update are decoded and averaged on the device in one launch (each client's
-        level and sign planes read once, no decoded copy materialised): summed in torch's CPU order for
-        ``torch.sum(torch.stack(...), dim=0)`` (csrc/torch_sum_order.h), then / K, bit-identical to
-        simple_aggregate of the decoded CPU tensors at every K (tests/golden/aggregate.npz: the reference's
-        own payloads and aggregates at K = 5, 8, 16, 20). Everything else (biases, running statistics, empty
-        tensors) is decoded and aggregated as the reference does, on the host."""
-        if not all_c_params:
-            raise AssertionError("receive_mean: no updates")   # simple_aggregate asserts len > 0
-        for c in all_c_params:
-            assert isinstance(c, QuantParameters)
-        s_time = time.perf_counter()
-        names = list(all_c_params[0].params.keys())
-        order_ok = device_mean_order_ok()
-        out: Parameters = {}
-        fast = self._mean_host_updates(all_c_params, names) if order_ok else None
-        if fast is not None:   # every update a CPU dict of the same entries: classified in native calls
-            fused, decoded = fast
-            out.update(zip(fused, decoded))
-        else:
-            fused = [n for n in names if all(n in c.params and self._fusable(c.params[n]) for c in all_c_params)
-                     and len({tuple(c.params[n].data.shape) for c in all_c_params}) == 1] if order_ok else []
-            if fused:
-                out.update(zip(fused, _decode_mean_stoch(all_c_params, fused, self.CODEC, self.bits)))
-        rest = [n for n in names if n not in out]
-        if rest:
-            parts = [self._receive(QuantParameters({n: c.params[n] for n in rest}, 0))[0] for c in all_c_params]
-            out.update(_aggregate_entries(rest, parts))
-        return {n: out[n] for n in names}, time.perf_counter() - s_time
-
-    def receive_add_(self, c_params: CompressedParameters, targets: List[Parameters]) -> float:
-        """``on_client_receive(c_params)`` followed by ``add_parameters_inpace(t, decoded, 1, 1, False)`` for
-        every ``t`` in ``targets`` — the client pool's ``add_to_model`` / ``add_to_model_all``
-        (Src/ADFL/Client/pool.py:62-75) and QAFeL's hidden-state update (Src/ADFL/Server/qafel.py:176-179),
-        bit-identical to them. Returns the seconds spent.
-
-        Encoded tensors whose targets are all fp32 device tensors are decoded once, into device memory, and
-        added into every model there (no decoded tensor crosses PCIe). Everything else takes the reference's
-        route: decode, then ``mul_(1).add_(decoded, alpha=1)``."""
-        assert isinstance(c_params, QuantParameters)
-        for t in targets:
-            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
-        s_time = time.perf_counter()
+    def _add_fused(self, c_params: QuantParameters, targets: List[Parameters]) -> List[str]:
         fused = [n for n, p in c_params.params.items()
                  if self._fusable(p) and all(t[n].is_cuda and t[n].dtype == torch.float32 for t in targets)]
         if fused and targets:
             dev = targets[0][fused[0]].device   # the staging's device (the current one) for the whole set
-            if dev.index == torch.cuda.current_device() and all(t[n].device == dev for t in targets for n in fused):
-                _decode_add_stoch([(n, c_params.params[n]) for n in fused], self.CODEC, self.bits,
-                                  [[t[n] for n in fused] for t in targets])
-            else:
-                fused = []
-        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in fused}, 0)
-        if rest.params:
-            decoded, _ = self.on_client_receive(rest)
-            with torch.no_grad():
-                for t in targets:
-                    for n, d in decoded.items():
-                        t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
-        return time.perf_counter() - s_time
+            if dev.index != torch.cuda.current_device() or any(t[n].device != dev for t in targets for n in fused):
+                return []
+        return fused
+
+    def _decode_add(self, c_params: QuantParameters, names: List[str], targets: List[Parameters]) -> None:
+        if targets:
+            _decode_add_stoch([(n, c_params.params[n]) for n in names], self.CODEC, self.bits,
+                              [[t[n] for n in names] for t in targets])
+
+    def _mean_payloads(self, all_c_params: List[QuantParameters], names: List[str]) -> List[torch.Tensor]:
+        return _decode_mean_stoch(all_c_params, names, self.CODEC, self.bits)
+
+    @staticmethod
+    def _mean_shape(p: QuantParameter):
+        return p.data.shape
 
     def _mean_host_updates(self, all_c_params: List[QuantParameters], names: List[str]):
         """receive_mean's common case in a few native calls: K updates of one model whose entries come in the
         same order and whose every non-empty ndim > 1 entry is a pair of contiguous CPU byte planes of one
-        element count and, across updates, one shape. Returns (those names, their means), or None when the
-        updates are anything else (receive_mean then classifies entry by entry)."""
+        element count and, across updates, one shape. Returns (those names, their means, no passthrough names:
+        the other entries all go through _receive), or None when the updates are anything else (receive_mean
+        then classifies entry by entry)."""
         if any(list(c.params.keys()) != names for c in all_c_params):
             return None
         th = _torchhost.get()
@@ -789,7 +719,7 @@ class _StochChannel(Channel):
             return None
         idx = np.nonzero((ndim > 1) & (numel > 0))[0].tolist()
         if not idx:
-            return [], []
+            return [], [], []
         lv = [[d[i] for i in idx] for d in datas]
         sg = [[c[i].signs for i in idx] for c in ps]
         lvm = [th.byte_planes(x) for x in lv]
@@ -805,7 +735,7 @@ class _StochChannel(Channel):
         means = _decode_mean_stoch_host(lv[0], n0, [m[2].numpy().view(np.uint64) for m in lvm],
                                         [m[2].numpy().view(np.uint64) for m in sgm], norms, mins, self.CODEC,
                                         self.bits)
-        return [names[i] for i in idx], means
+        return [names[i] for i in idx], means, []
 
     @staticmethod
     def _fusable(p: QuantParameter) -> bool:
@@ -842,18 +772,9 @@ class _StochChannel(Channel):
             size[0] += f32_numel[k]   # one byte per element
 
         pass_signs = torch.zeros(1, dtype=torch.uint8)  # passthrough entries' unused signs, one per call
-        rest = iter([items[i] for i in np.nonzero(ndim <= 1)[0].tolist()])
-
-        def idle(batch=32):   # passthrough entries, a batch per staging range
-            for _ in range(batch):
-                e = next(rest, None)
-                if e is None:
-                    return False
-                t = e[1]
-                made[e[0]] = qp(t, bits, 0, pass_signs, t.shape, t.dtype, t.dtype, 0)
-                size[0] += t.nbytes
-            return True
-
+        # passthrough entries (scale 0, scale_2 0), a batch per staging range
+        idle = _passthrough_idle([items[i] for i in np.nonzero(ndim <= 1)[0].tolist()], made, size, bits, 0,
+                                 pass_signs, 0)
         encoded = (_encode_stoch(params, f32, self.CODEC, bits, uniforms if uniforms is None or
                                  uniforms.dtype == torch.float32 else None, seed, tn, emit=emit, idle=idle)
                    if f32 else {})
@@ -903,17 +824,6 @@ class CNATChannel(_StochChannel):
     """Bi-directional natural compression (quant.py:426-545): stochastic power-of-two exponents."""
 
     CODEC = "cnat"
-
-
-class _Unidirectional:
-    """Only client -> server is compressed; server -> client and the client's receive use the identity
-    channel (quant.py:255-277,401-423,548-570)."""
-
-    def on_server_send(self, params: Parameters) -> Tuple[CompressedParameters, float]:
-        return IdentityChannel(no_compute_time=True).on_server_send(params)
-
-    def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
-        return IdentityChannel(no_compute_time=True).on_client_receive(c_params)
 
 
 class UQSGDChannel(_Unidirectional, QSGDChannel):

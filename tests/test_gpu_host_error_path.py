@@ -1,6 +1,6 @@
 """GPU: a range-pipelined host-to-host channel call that fails part-way — an output allocation
 raising while the later ranges' H2D, kernels and D2H are still queued — waits for that device work before the
-exception leaves (quant._drain), so the next call, which gathers into the same pinned and device staging
+exception leaves (_staging._drain), so the next call, which gathers into the same pinned and device staging
 buffers, returns exactly what a call on a clean channel returns.
 
 The failure is injected into the native output-creation call of the second staging range (adfl_torchhost's
@@ -16,7 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from adfl_amd import _torchhost  # noqa: E402
-from adfl_amd.Channel import quant  # noqa: E402
+from adfl_amd.Channel import _staging  # noqa: E402
 from adfl_amd.Channel.quant import CNATChannel, QSGDChannel, SLQChannel  # noqa: E402
 
 
@@ -81,9 +81,9 @@ def _same_dict(a, b):
 
 
 def _assert_drained():
-    """quant._drain's guarantee when the exception leaves: nothing is queued or running on the compute stream or
+    """_staging._drain's guarantee when the exception leaves: nothing is queued or running on the compute stream or
     the staging copy streams (asked before any synchronize or further GPU call, which would hide queued work)."""
-    st = quant._staging()
+    st = _staging._staging()
     assert torch.cuda.current_stream().query(), "compute stream still busy after the failed call"
     assert st.d2h_stream().query(), "D2H stream still busy after the failed call"
     assert st.h2d_stream().query(), "H2D stream still busy after the failed call"

@@ -17,7 +17,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from adfl_amd import _lib, ops  # noqa: E402
-from adfl_amd.Channel import quant  # noqa: E402
+from adfl_amd.Channel import _staging, quant  # noqa: E402
 
 DEV = torch.device("cuda", 0)
 E_ARG = -1
@@ -51,7 +51,7 @@ def test_encode_ranges_match_one_launch(sizes, nranges):
     s_dev = torch.full((lay.ntensors,), -1.0, device=DEV)
     part_dev = torch.full((lay.nchunks,), -1, dtype=torch.int32, device=DEV)
     chunks = lay.device_chunks(DEV)
-    cm = quant._chunk_meta(lay)
+    cm = _staging._chunk_meta(lay)
     ends = lay.offsets + lay.sizes
     evs = (ctypes.c_void_p * (2 * nranges))()
     assert lib.adfl_stage_events_create(2 * nranges, evs) == 0
@@ -104,7 +104,7 @@ def test_decode_ranges_match_one_launch(sizes, nranges):
     out_host = torch.full((lay.total,), float("nan")).pin_memory()
     s_dev = scales.to(DEV)
     chunks = lay.device_chunks(DEV)
-    cm = quant._chunk_meta(lay)
+    cm = _staging._chunk_meta(lay)
     evs = (ctypes.c_void_p * (2 * nranges))()
     assert lib.adfl_stage_events_create(2 * nranges, evs) == 0
     side = torch.cuda.Stream(DEV)
@@ -198,7 +198,7 @@ def test_stoch_decode_ranges_match_one_launch(codec, sizes, nranges):
     out_h = torch.full((lay.total,), float("nan")).pin_memory()
     n_d, m_d = norms.to(DEV), mins.to(DEV)
     chunks = lay.device_chunks(DEV)
-    cm = quant._chunk_meta(lay)
+    cm = _staging._chunk_meta(lay)
     evs = (ctypes.c_void_p * (2 * nranges))()
     assert lib.adfl_stage_events_create(2 * nranges, evs) == 0
     side = torch.cuda.Stream(DEV)
@@ -254,9 +254,9 @@ def test_stoch_host_encode_ranges_match_whole_bucket(cls, monkeypatch):
     params = {f"w{i}": torch.randn(1, n, generator=g) * 1e-2 for i, n in enumerate(sizes)}
     params["w3"].zero_()
     params["b"] = torch.randn(10, generator=g)
-    monkeypatch.setattr(quant, "_PIECE_BYTES", 1 << 16)   # many ranges
+    monkeypatch.setattr(_staging, "_PIECE_BYTES", 1 << 16)   # many ranges
     got = ch._quantize_params(params, 8, seed=1234)
-    monkeypatch.setattr(quant, "_PIPELINE", False)
+    monkeypatch.setattr(_staging, "_PIPELINE", False)
     want = ch._quantize_params(params, 8, seed=1234)
     for n in params:
         a, b = got.params[n], want.params[n]

@@ -126,14 +126,14 @@ def test_receive_mean_falls_back_when_torch_sums_in_another_order(channel, monke
     one aggregate must not disagree)."""
     import importlib
     from adfl_amd import sum_order
-    from adfl_amd.Channel import quant
+    from adfl_amd.Channel import _base
     C = importlib.import_module("adfl_amd.Channel")
     ch = getattr(C, channel)(8)
     updates = [ch.on_client_send(_client(r))[0] for r in range(5)]
     decoded = [ch.on_server_receive(u)[0] for u in updates]
     want = simple_aggregate(decoded)
     monkeypatch.setattr(sum_order, "self_check", lambda: False)
-    monkeypatch.setattr(quant, "_ORDER_WARNED", [False])
+    monkeypatch.setattr(_base, "_ORDER_WARNED", [False])
     with pytest.warns(RuntimeWarning, match="sum order"):
         got, _ = ch.receive_mean(updates)
     for n in want:

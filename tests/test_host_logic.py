@@ -223,7 +223,7 @@ def test_aggregate_entries_matches_simple_aggregate(k):
     (Src/ADFL/model.py:221-234) entry by entry, bit for bit: fp32 of every tail shape, int64 counters (-> fp32),
     one-element entries, empty and fp16 entries (per entry through torch)."""
     import torch
-    from adfl_amd.Channel import quant
+    from adfl_amd.Channel import _base
     g = torch.Generator().manual_seed(k)
     names = [f"b{i}" for i in range(40)] + ["cnt", "one", "e", "h"]
     parts = []
@@ -232,8 +232,8 @@ def test_aggregate_entries_matches_simple_aggregate(k):
         p.update(cnt=torch.tensor(5 + r, dtype=torch.int64), one=torch.randn(1, generator=g), e=torch.empty(0),
                  h=torch.randn(3, generator=g).half())
         parts.append(p)
-    got = quant._aggregate_entries(names, parts)
+    got = _base._aggregate_entries(names, parts)
     for n in names:
-        want = quant._simple_aggregate([p[n] for p in parts])
+        want = _base._simple_aggregate([p[n] for p in parts])
         assert got[n].dtype == want.dtype and got[n].shape == want.shape, n
         assert torch.equal(got[n].reshape(-1).view(torch.uint8), want.reshape(-1).view(torch.uint8)), n

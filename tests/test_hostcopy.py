@@ -71,29 +71,29 @@ def test_argument_errors():
 @pytest.mark.parametrize("sizes,piece", [([5, 3_000_000, 17, 65_536, 1], 1 << 20), ([1 << 22], 1 << 20),
                                          ([64] * 500 + [999_999], 1 << 16)])
 def test_channel_staging_ranges_cut_through_tensors(sizes, piece, align, monkeypatch):
-    """The Channel's host staging (Channel/quant.py _ranges / _range_copies): element ranges that cut through
+    """The Channel's host staging (Channel/_staging.py _ranges / _range_copies): element ranges that cut through
     tensors gather into the bucket and scatter back exactly, pads untouched, every element once."""
     from adfl_amd import ops
-    from adfl_amd.Channel import quant
-    monkeypatch.setattr(quant, "_PIECE_BYTES", piece)
+    from adfl_amd.Channel import _staging
+    monkeypatch.setattr(_staging, "_PIECE_BYTES", piece)
     lay = ops.BucketLayout(sizes, align=align)
     rng = np.random.default_rng(7)
     srcs = [torch.from_numpy(rng.standard_normal(n).astype(np.float32)) for n in sizes]
     bucket = torch.full((lay.total,), -7.0)
-    ranges = quant._ranges(lay, 4)
+    ranges = _staging._ranges(lay, 4)
     assert ranges[0][0] == 0 and ranges[-1][1] == lay.total
     assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
-    ptrs = quant._ptrs(srcs)
+    ptrs = _staging._ptrs(srcs)
     for lo, hi in ranges:
-        hostcopy.copy_pieces(*quant._range_copies(ptrs, lay, bucket.data_ptr(), 4, lo, hi, to_bucket=True))
+        hostcopy.copy_pieces(*_staging._range_copies(ptrs, lay, bucket.data_ptr(), 4, lo, hi, to_bucket=True))
     want = np.full(lay.total, -7.0, np.float32)
     for s, o in zip(srcs, lay.offsets):
         want[o:o + s.numel()] = s.numpy()
     assert np.array_equal(bucket.numpy(), want)
     outs = [torch.empty(n) for n in sizes]
-    optr = quant._ptrs(outs)
+    optr = _staging._ptrs(outs)
     for lo, hi in reversed(ranges):
-        hostcopy.copy_pieces(*quant._range_copies(optr, lay, bucket.data_ptr(), 4, lo, hi, to_bucket=False))
+        hostcopy.copy_pieces(*_staging._range_copies(optr, lay, bucket.data_ptr(), 4, lo, hi, to_bucket=False))
     for a, b in zip(outs, srcs):
         assert torch.equal(a, b)
 

@@ -1,7 +1,7 @@
 """Per-phase wall time of SLQChannel's host-to-host path on the C3 dict (256 weights + 256 biases, CPU
 tensors): where the milliseconds of on_client_send / on_server_receive go. Each phase is synchronised
 separately, so the phases add up to more than the real (overlapped) call. Phases follow the current code
-(Channel/quant.py: _stage_in / _stage_out over the native copy pool, csrc/host_copy.cpp).
+(Channel/_staging.py: _stage_in / _stage_out over the native copy pool, csrc/host_copy.cpp).
 
     python tools/channel_breakdown.py
 """
@@ -16,7 +16,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "ad-federatedlearning_amd"))
 from adfl_amd import hostcopy, ops  # noqa: E402
 from adfl_amd.Channel import SLQChannel  # noqa: E402
-from adfl_amd.Channel.quant import _int8_view, _stage_out, _staging  # noqa: E402
+from adfl_amd.Channel._staging import _int8_view, _stage_out, _staging  # noqa: E402
 
 
 def main():

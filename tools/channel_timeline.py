@@ -17,7 +17,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "ad-federatedlearning_amd"))
 from adfl_amd import hostcopy  # noqa: E402
 from adfl_amd.Channel import SLQChannel  # noqa: E402
-from adfl_amd.Channel import quant  # noqa: E402
+from adfl_amd.Channel import _staging, quant  # noqa: E402
 
 STAMPS = []
 
@@ -37,16 +37,17 @@ def wrap(obj, name, label):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--calls", type=int, default=30)
-    p.add_argument("--no-pipeline", action="store_true", help="quant._PIPELINE off (create all outputs, then scatter)")
+    p.add_argument("--no-pipeline", action="store_true", help="_staging._PIPELINE off (create all outputs, then scatter)")
     args = p.parse_args()
     if args.no_pipeline:
-        quant._PIPELINE = False
+        _staging._PIPELINE = False
+    # functions are wrapped under the name their caller uses (quant's imported _stage_in), classes where defined
     for obj, name, label in [(quant, "_stage_in", "stage_in (gather + H2D enqueue)"),
                              (quant.ops, "encode_batched", "encode kernel enqueue"),
                              (quant.ops, "decode_batched", "decode kernel enqueue"),
-                             (quant._PendingD2H, "__init__", "D2H enqueue"),
-                             (quant._PendingD2H, "finish", "wait D2H + scatter"),
-                             (quant._PendingD2H, "finish_building", "create outputs + pipelined scatter"),
+                             (_staging._PendingD2H, "__init__", "D2H enqueue"),
+                             (_staging._PendingD2H, "finish", "wait D2H + scatter"),
+                             (_staging._PendingD2H, "finish_building", "create outputs + pipelined scatter"),
                              (hostcopy, "advise_huge", "advise_huge"),
                              (hostcopy.Pending, "wait", "native job wait"),
                              (quant, "_host_scales", "host scales (range landed, H2D enqueued)"),
