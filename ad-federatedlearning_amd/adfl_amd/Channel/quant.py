@@ -201,7 +201,6 @@ def _encode_dict(params: Parameters, names: List[str], bits: int, stats: Optiona
     scale) is called for each as it is created and idle() (returning True while it has work left) between
     the copy ranges."""
     st = _staging()
-    dev = st.device
     tensors = [params[n] for n in names]
     # meta: (sizes, all contiguous CPU) from _quantize_params' native scan (every tensor already fp32)
     lay = st.layout(meta[0] if meta is not None else tuple(int(t.numel()) for t in tensors))
@@ -217,6 +216,14 @@ def _encode_dict(params: Parameters, names: List[str], bits: int, stats: Optiona
     if stats is not None:
         stats.append(_qerror_sums(x_dev, ops.decode_batched(q_dev, s_dev, lay, out=st.buf("qe_d", lay.total, torch.float32)),
                                   lay))
+    return _payloads_out(names, tensors, lay, st, q_dev, s_dev)
+
+
+def _payloads_out(names: List[str], tensors: List[torch.Tensor], lay: ops.BucketLayout, st: _DeviceStaging,
+                  q_dev: torch.Tensor, s_dev: torch.Tensor):
+    """The owned qint8 payloads of an encoded bucket (q_dev, s_dev in `lay`): {name: (qint8 tensor shaped like
+    tensors[k] and on its device, python float scale)} — the output half of _encode_dict and _encode_delta_dict."""
+    dev = st.device
     scales_host = st.buf("scales_host", lay.ntensors, torch.float32, pinned=True)
     scales_host.copy_(s_dev, non_blocking=True)
     on_cpu = [not t.is_cuda for t in tensors]
@@ -436,7 +443,6 @@ def _encode_dict_packed(params: Parameters, names: List[str], bits: int, stats: 
     """Packed int4 variant of _encode_dict: {name: (int8 tensor of ceil(n/2) packed bytes, scale)}; with
     `stats`, the bucket's four q-error sums against its packed payload are appended."""
     st = _staging()
-    dev = st.device
     tensors = [params[n] for n in names]
     th = _torchhost.get()
     host_ok, numel, hptrs = th.host_bytes(tensors, 4)   # sizes, and contiguous CPU fp32 storages, in one call
@@ -448,12 +454,33 @@ def _encode_dict_packed(params: Parameters, names: List[str], bits: int, stats: 
     if stats is not None:
         stats.append(_qerror_sums(x_dev, ops.decode_batched_int4(p_dev, s_dev, lay,
                                                                  out=st.buf("qe_d", lay.total, torch.float32)), lay))
+    return _packed_out(names, tensors, lay, st, p_dev, s_dev, host_ok, numel)
+
+
+def _packed_bytes_layout(lay: ops.BucketLayout, st: _DeviceStaging) -> ops.BucketLayout:
+    """The packed-byte layout of an even-offset element layout: tensor k's ceil(n/2) bytes at offsets[k] / 2.
+    With align=2 every slot is exactly that many bytes and the layout is the compact one of the staging cache;
+    a wider alignment (send_delta's device route) keeps its pads out of the layout (cached on `lay`)."""
+    if lay.align == 2:
+        return st.layout(tuple(int(n) // 2 for n in lay.padded.tolist()), align=1)
+    p_lay = lay.__dict__.get("_packed_bytes")
+    if p_lay is None:
+        p_lay = lay.__dict__["_packed_bytes"] = ops.BucketLayout(((lay.sizes + 1) // 2).tolist(),
+                                                                 offsets=(lay.offsets // 2).tolist())
+    return p_lay
+
+
+def _packed_out(names: List[str], tensors: List[torch.Tensor], lay: ops.BucketLayout, st: _DeviceStaging,
+                p_dev: torch.Tensor, s_dev: torch.Tensor, host_ok: bool, numel: torch.Tensor):
+    """The owned packed payloads of an int4-encoded bucket: {name: (int8 tensor of ceil(n/2) packed bytes on
+    tensors[k]'s device, python float scale)} — the output half of _encode_dict_packed and _encode_delta_dict_packed."""
+    dev = st.device
+    th = _torchhost.get()
     scales_host = st.buf("scales_host", lay.ntensors, torch.float32, pinned=True)
     scales_host.copy_(s_dev, non_blocking=True)
     torch.cuda.current_stream(dev).synchronize()
     scales = scales_host.tolist()
-    # packed-byte layout: with align=2 tensor k's ceil(n/2) bytes sit at offsets[k] / 2
-    p_lay = st.layout(tuple(int(n) // 2 for n in lay.padded.tolist()), align=1)
+    p_lay = _packed_bytes_layout(lay, st)
     if host_ok:   # the owned int8 payloads created by one native call per staging range while the D2H runs
         p_numel = (numel + 1) // 2
         parts = _PendingD2H(p_dev.view(torch.int8), p_lay, st, "p").finish_building(
@@ -484,6 +511,109 @@ def _decode_dict_packed(items: List[Tuple[str, torch.Tensor, torch.Size, float]]
     out_dev = ops.decode_batched_int4(p_dev, s_dev, lay, out=st.buf("d_out", lay.total, torch.float32))
     decoded = _hand_out(out_dev, lay, [torch.Size(shape) for _, _, shape, _ in items], on_cpu, st, "d_out")
     return {name: t for (name, _, _, _), t in zip(items, decoded)}
+
+
+def _delta_on_device(prevs: List[torch.Tensor], news: List[torch.Tensor], dev: torch.device):
+    """(new's, prev's data pointers as CPU int64 tensors) when every tensor of both lists is a contiguous
+    4-byte-element tensor on the staging device (fp32: _delta_pairs saw to the dtype) — the pointer-table
+    route — else None. One native call per list (adfl_torchhost.device_ptrs)."""
+    th = _torchhost.get()
+    ok_n, _, n_ptrs = th.device_ptrs(news, dev.index, 4)
+    if not ok_n:
+        return None
+    ok_p, _, p_ptrs = th.device_ptrs(prevs, dev.index, 4)
+    return (n_ptrs, p_ptrs) if ok_p else None
+
+
+@_serialized
+def _encode_delta_dict(prevs: List[torch.Tensor], news: List[torch.Tensor], names: List[str], bits: int):
+    """SLQ-encode news[k] - prevs[k] (fp32, ndim > 1, equal shapes) for every k without materialising the
+    difference: {name: (qint8 tensor shaped like news[k] and on its device, python float scale)}.
+
+    Device dicts: the kernels read the tensors through two pointer tables (no bucket of either source and none
+    of the difference exists), the payload goes to a 64-element-aligned bucket, so separately allocated
+    tensors take the 16-byte path, and the qint8 outputs are filled from it by one scatter launch. CPU or mixed
+    dicts: each dict is staged as a compact device bucket (two H2D copies; diffing on the host inside the
+    gather, to keep one, is not done), the same kernels run over the two buckets, and the payloads come back
+    through the D2H + scatter path of _encode_dict."""
+    st = _staging()
+    dev = st.device
+    sizes = tuple(int(t.numel()) for t in news)
+    ptrs = _delta_on_device(prevs, news, dev)
+    if ptrs is not None:
+        lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
+        src_new, src_prev = news, prevs
+    else:
+        lay = st.layout(sizes, align=1)
+        src_new = _stage_in(news, lay, st, "x", torch.float32)
+        src_prev = _stage_in(prevs, lay, st, "x_prev", torch.float32)
+    q_dev, s_dev = ops.encode_delta_batched(src_new, src_prev, lay, bits, ptrs=ptrs,
+                                            q=st.buf("q", lay.total, torch.int8),
+                                            scales=st.buf("scales", lay.ntensors, torch.float32),
+                                            partials=st.buf("partials", lay.nchunks, torch.int32))
+    return _payloads_out(names, news, lay, st, q_dev, s_dev)
+
+
+@_serialized
+def _encode_delta_dict_packed(prevs: List[torch.Tensor], news: List[torch.Tensor], names: List[str], bits: int):
+    """Packed int4 variant of _encode_delta_dict: {name: (int8 tensor of ceil(n/2) packed bytes, scale)}."""
+    st = _staging()
+    dev = st.device
+    th = _torchhost.get()
+    host_ok, numel, hptrs = th.host_bytes(news, 4)   # sizes, and contiguous CPU fp32 storages, in one call
+    sizes = tuple(numel.tolist())
+    ptrs = _delta_on_device(prevs, news, dev)
+    if ptrs is not None:
+        lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
+        src_new, src_prev = news, prevs
+    else:
+        lay = st.layout(sizes, align=2)
+        src_new = _stage_in(news, lay, st, "x", torch.float32,
+                            host_ptrs=hptrs.numpy().view(np.uint64) if host_ok else None)
+        src_prev = _stage_in(prevs, lay, st, "x_prev", torch.float32)
+    p_dev, s_dev = ops.encode_delta_batched_int4(src_new, src_prev, lay, bits, ptrs=ptrs,
+                                                 packed=st.buf("p", lay.total // 2, torch.uint8),
+                                                 scales=st.buf("scales", lay.ntensors, torch.float32),
+                                                 partials=st.buf("partials", lay.nchunks, torch.int32))
+    return _packed_out(names, news, lay, st, p_dev, s_dev, host_ok, numel)
+
+
+def _delta_pairs(params_prev: Parameters, params_new: Parameters):
+    """diff_parameters' view of a dict pair (Src/ADFL/model.py:350-358) without the difference of the ndim > 1
+    entries: (names in params_prev's order, {name: new - prev} for the ndim <= 1 entries, and for the others
+    the fp32 (prev, new) tensors to encode), raising what the reference raises on the way: the key-set
+    assertion, torch's error for shapes `new - prev` cannot broadcast, and quantize's errors for an ndim > 1
+    difference that would be empty or not fp32. A pair on two devices takes params_new's (plain torch would
+    refuse it)."""
+    assert set(params_prev.keys()) == set(params_new.keys())
+    names = list(params_prev.keys())
+    plain: Dict[str, torch.Tensor] = {}
+    pairs: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+    batch: List[str] = []   # ndim <= 1 pairs of one shape, dtype and device: subtracted together below
+    with torch.no_grad():
+        for n in names:
+            a, b = params_prev[n], params_new[n]
+            if a.shape == b.shape and a.ndim > 1:
+                pairs[n] = (a, b)
+            elif a.shape == b.shape and a.dtype == b.dtype and a.device == b.device:
+                batch.append(n)
+            else:
+                d = b - (a if a.device == b.device else a.to(b.device))
+                if a.shape != b.shape and d.ndim > 1:   # broadcastable, but not one model's two states
+                    raise RuntimeError(f"send_delta: '{n}' has shape {tuple(a.shape)} in params_prev and "
+                                       f"{tuple(b.shape)} in params_new")
+                plain[n] = d
+        if batch:   # torch's own subtraction, each result its own tensor on its own device, a few launches in all
+            plain.update(zip(batch, torch._foreach_sub([params_new[n] for n in batch],
+                                                       [params_prev[n] for n in batch])))
+        f32 = torch.float32
+        for n, (a, b) in pairs.items():   # quant.py:100-103 on the difference: its dtype is torch's promotion
+            dt = a.dtype if a.dtype == b.dtype else torch.result_type(b, a)
+            if dt != f32 or b.numel() == 0:
+                ops.require_quantizable(torch.empty(b.shape, dtype=dt, device="meta"))
+            if a.dtype != dt or b.dtype != dt:   # e.g. fp16 - fp32: torch converts exactly, then subtracts
+                pairs[n] = (a.to(dt), b.to(dt))
+    return names, plain, pairs
 
 
 class SLQChannel(_CodecChannel):
@@ -599,6 +729,41 @@ class SLQChannel(_CodecChannel):
         rel_mse, cos = qerror.metrics(e, s, c, count)
         return q_params, c_time, rel_mse, cos
 
+    def send_delta(self, params_prev: Parameters, params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``on_client_send(diff_parameters(params_prev, params_new))`` — what every CommType.DELTA strategy
+        sends (the clients, Src/ADFL/Client/async_sc.py:106-114,318-324; QAFeL's server,
+        Src/ADFL/Server/qafel.py:160-161) — with the difference of the ndim > 1 tensors formed inside the encode
+        kernels and never written (ops.encode_delta_batched). Returns (c_params, seconds); c_params equals the
+        two-step result bit for bit and field for field (payload, scale, shape, dtypes, bits, size), in
+        params_prev's key order (model.py:356). ndim <= 1 entries carry ``new - prev`` computed by torch on
+        their own device, with scale 1. Neither input is modified. The same errors are raised: the key-set
+        assertion, torch's for shapes that do not match, quantize's for an ndim > 1 entry that is empty or
+        whose difference is not fp32."""
+        s_time = time.perf_counter()
+        q_params = self._quantize_delta(params_prev, params_new, self.bits)
+        return q_params, time.perf_counter() - s_time
+
+    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int) -> QuantParameters:
+        names, plain, pairs = _delta_pairs(params_prev, params_new)
+        qnames = list(pairs)
+        encoded = _encode_delta_dict([pairs[n][0] for n in qnames], [pairs[n][1] for n in qnames], qnames,
+                                     bits) if qnames else {}
+        signs = torch.zeros(1, dtype=torch.uint8)  # the unused field (quant.py:91), one object per call
+        qp = QuantParameter
+        out: Dict[str, QuantParameter] = {}
+        size = 0
+        for n in names:
+            # positional: QuantParameter(data, bits, scale, signs, shape, dtype, q_dtype) (model.py:21-31)
+            if n in encoded:
+                q, scale = encoded[n]
+                out[n] = qp(q, bits, scale, signs, q.shape, torch.float32, torch.qint8)
+                size += q.numel()             # a qint8 payload: one byte per element
+            else:
+                t = plain[n]                  # passthrough (quant.py:80-81: scale 1)
+                out[n] = qp(t, bits, 1, signs, t.shape, t.dtype, t.dtype)
+                size += t.nbytes
+        return QuantParameters(out, size)
+
     def _quantize_params(self, params: Parameters, bits: int, stats: Optional[list] = None) -> QuantParameters:
         """Biases and running metrics (ndim <= 1) are not quantized (quant.py:74-94)."""
         items = list(params.items())
@@ -684,6 +849,26 @@ class PackedSLQChannel(SLQChannel):
         return _decode_mean([[c.params[n].data for n in names] for c in all_c_params],
                             [[c.params[n].scale for n in names] for c in all_c_params],
                             [torch.Size(all_c_params[0].params[n].shape) for n in names], packed=True)
+
+    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int) -> QuantParameters:
+        names, plain, pairs = _delta_pairs(params_prev, params_new)
+        qnames = list(pairs)
+        encoded = _encode_delta_dict_packed([pairs[n][0] for n in qnames], [pairs[n][1] for n in qnames], qnames,
+                                            bits) if qnames else {}
+        signs = torch.zeros(1, dtype=torch.uint8)  # the unused field (compression.py:102), one object per call
+        qp = QuantParameter
+        out: Dict[str, QuantParameter] = {}
+        size = 0
+        for n in names:
+            if n in encoded:
+                q_param, scale = encoded[n]
+                shape, dtype = pairs[n][1].shape, torch.float32
+            else:
+                q_param, scale = plain[n], 1
+                shape, dtype = q_param.shape, q_param.dtype
+            out[n] = qp(q_param, bits, scale, signs, shape, dtype, q_param.dtype)
+            size += q_param.nbytes
+        return QuantParameters(out, size)
 
     def _quantize_params(self, params: Parameters, bits: int, stats: Optional[list] = None) -> QuantParameters:
         items = list(params.items())

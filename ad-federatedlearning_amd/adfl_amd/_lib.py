@@ -23,7 +23,8 @@ INT = ctypes.c_int
 ALIGN_ELEMS = 64     # ADFL_SLQ_ALIGN_ELEMS
 CHUNK_ELEMS = 8192   # ADFL_SLQ_CHUNK_ELEMS
 RESIDENT_CHUNKS = 8  # ADFL_SLQ_RESIDENT_CHUNKS
-ABI_VERSION = 2      # ADFL_SLQ_ABI_VERSION
+DELTA_RESIDENT_CHUNKS = 8  # ADFL_SLQ_DELTA_RESIDENT_CHUNKS
+ABI_VERSION = 3      # ADFL_SLQ_ABI_VERSION
 
 
 class AdflError(RuntimeError):
@@ -69,6 +70,10 @@ SIGNATURES = {
     "adfl_slq_dequantize_add_batched": (INT, [P, P, I64, P, P, I32, I32, P]),
     "adfl_slq_dequantize_mean_batched": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
     "adfl_slq_dequantize_mean_batched_int4": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
+    "adfl_slq_encode_delta_batched": (INT, [P, P, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_batched_int4": (INT, [P, P, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_batched_int4_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
     # adfl_stoch.h
     "adfl_stoch_workspace_bytes": (I64, [I64]),
     "adfl_stoch_norms_batched": (INT, [P, P, I64, INT, P, I64, P, P, P]),

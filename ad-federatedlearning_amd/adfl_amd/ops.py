@@ -8,13 +8,15 @@ synchronises. Semantics are the reference's, bit for bit:
 * ``encode_batched`` / ``decode_batched`` — the per-tensor loop of ``_quantize_params`` / ``_receive``
   (quant.py:67-94) as one launch per pass over a whole bucketed state dict
 * ``encode_int4`` / ``decode_int4`` / ``pack_int4`` / ``unpack_int4`` — Src/ADFL/compression.py:35-66
+* ``encode_delta_batched`` / ``encode_delta_batched_int4`` — ``diff_parameters(prev, new)`` (Src/ADFL/model.py:350-358)
+  followed by the same per-tensor encode, the difference formed in registers and never written
 * ``dequantize_mean`` — the peer mean after the exchange (Examples/ray_ad.py:188); ``dequantize_mean_batched``
   the same over bucketed payloads with per-tensor scales
 
 The same ops are registered as PyTorch custom ops ``torch.ops.adfl.*`` (with fake implementations, so
 they trace under torch.compile) at the bottom of this file: slq_absmax, slq_encode / slq_decode,
 slq_encode_int4 / slq_decode_int4, slq_encode_batched / slq_decode_batched and their _int4 variants over
-caller-placed tensors (host offsets / sizes), pack_int4 / unpack_int4, slq_dequantize_mean and
+caller-placed tensors (host offsets / sizes), slq_encode_delta_batched (+ _int4) over two such flat buffers, pack_int4 / unpack_int4, slq_dequantize_mean and
 slq_dequantize_mean_batched (+ _int4).
 """
 
@@ -533,6 +535,109 @@ def encode_batched_int4(flat: torch.Tensor, layout: BucketLayout, bits: int = 4,
     return packed, scales
 
 
+def _delta_sources(src, layout: BucketLayout, dev: torch.device, what: str):
+    """One source of a delta encode as (device int64 table of one fp32 pointer per tensor, what keeps them alive).
+    `src` is one flat fp32 device buffer holding tensor t at layout.offsets[t] (pointer t = base + offset t), or
+    a sequence of contiguous fp32 device tensors of the layout's sizes. No alignment beyond fp32's own."""
+    if isinstance(src, torch.Tensor):
+        if src.dtype != torch.float32:
+            raise RuntimeError(f"Quantize only works on Float Tensor, got {_TORCH_TYPE_NAMES.get(src.dtype, src.dtype)}")
+        if not src.is_cuda or src.device != dev:
+            raise ValueError(f"adfl_amd.ops: {what} must be a device tensor on {dev}, got {src.device}")
+        flat = src.reshape(-1)
+        if not flat.is_contiguous():
+            flat = flat.contiguous()
+        if flat.numel() < layout.total:
+            raise ValueError(f"encode_delta_batched: {what} is smaller than the layout")
+        ptrs = flat.data_ptr() + 4 * layout.offsets
+        keep = flat
+    else:
+        keep = list(src)
+        if len(keep) != layout.ntensors:
+            raise ValueError(f"encode_delta_batched: {what} has {len(keep)} tensors for a layout of {layout.ntensors}")
+        for t, (x, n) in enumerate(zip(keep, layout.sizes.tolist())):
+            if not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != dev:
+                raise ValueError(f"encode_delta_batched: {what}[{t}] must be a device tensor on {dev}")
+            if x.dtype != torch.float32:
+                raise RuntimeError("Quantize only works on Float Tensor, got "
+                                   f"{_TORCH_TYPE_NAMES.get(x.dtype, x.dtype)}")
+            if not x.is_contiguous() or x.numel() != n:
+                raise ValueError(f"encode_delta_batched: {what}[{t}] must be a contiguous tensor of {n} elements")
+        ptrs = np.fromiter((x.data_ptr() for x in keep), dtype=np.int64, count=len(keep))
+    if (ptrs % 4).any():
+        raise ValueError(f"encode_delta_batched: {what} holds an fp32 pointer that is not 4-byte aligned")
+    return torch.from_numpy(np.ascontiguousarray(ptrs, dtype=np.int64)).to(dev, non_blocking=True), keep
+
+
+def _delta_device(new, prev) -> torch.device:
+    first = new if isinstance(new, torch.Tensor) else (new[0] if len(new) else None)
+    if not isinstance(first, torch.Tensor) or not first.is_cuda:
+        raise ValueError("adfl_amd.ops: encode_delta_batched takes CUDA/HIP device tensors")
+    return first.device
+
+
+def _delta_nwork(layout: BucketLayout) -> int:
+    """The resident (one-launch) form's work-list length, or 0 for the two passes: every tensor within
+    ADFL_SLQ_DELTA_RESIDENT_CHUNKS chunks, and ADFL_SLQ_ENCODE not forcing the two passes."""
+    if _encode_mode() == "twopass" or layout.max_tensor_chunks > _lib.DELTA_RESIDENT_CHUNKS:
+        return 0
+    return layout.nwork
+
+
+def _delta_tables(new, prev, layout: BucketLayout, dev: torch.device, ptrs):
+    """The two device pointer tables of a delta encode. ptrs: (new's, prev's) data pointers as CPU int64 tensors
+    when the caller has checked both tensor lists against the layout (the Channel: adfl_torchhost.device_ptrs)."""
+    if ptrs is not None:
+        if len(new) != layout.ntensors or len(prev) != layout.ntensors:
+            raise ValueError(f"encode_delta_batched: {len(new)} / {len(prev)} tensors for a layout of "
+                             f"{layout.ntensors}")
+        return ptrs[0].to(dev, non_blocking=True), ptrs[1].to(dev, non_blocking=True), None
+    n_tab, n_keep = _delta_sources(new, layout, dev, "new")
+    p_tab, p_keep = _delta_sources(prev, layout, dev, "prev")
+    return n_tab, p_tab, (n_keep, p_keep)   # the last: a contiguous copy of a strided flat buffer lives to the launch
+
+
+def encode_delta_batched(new, prev, layout: BucketLayout, bits: int, *, q: Optional[torch.Tensor] = None,
+                         scales: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None,
+                         ptrs=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``encode_batched`` of ``new - prev`` without writing the difference: diff_parameters (model.py:350-358)
+    then quant.py:74-104 per tensor, bit-identical to the two steps. `new` and `prev` are each one flat fp32
+    device buffer in `layout`, or a sequence of fp32 device tensors of its sizes (any addresses: sources that
+    are 16-byte aligned where the payload is take the vector path, others go element-wise with the same
+    result). Returns (int8 payload bucket in `layout`, per-tensor fp32 scales); neither input is modified.
+    ptrs: see _delta_tables (a caller that has already checked its tensor lists)."""
+    dev = _delta_device(new, prev)
+    n_tab, p_tab, _keep = _delta_tables(new, prev, layout, dev, ptrs)
+    q = _dst(q, layout.total, torch.int8, dev, "q")
+    scales = _dst(scales, layout.ntensors, torch.float32, dev, "scales", align=4)
+    partials = _dst(partials, layout.nchunks, torch.int32, dev, "partials", align=4)
+    check(_lib.load().adfl_slq_encode_delta_batched_work(
+        n_tab.data_ptr(), p_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        layout.device_work(dev).data_ptr(), _delta_nwork(layout), bits, q.data_ptr(), scales.data_ptr(),
+        partials.data_ptr(), _stream(dev)))
+    # the tables may be freed on return: the caching allocator only reuses them for later work on this stream
+    return q, scales
+
+
+def encode_delta_batched_int4(new, prev, layout: BucketLayout, bits: int = 4, *,
+                              packed: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
+                              partials: Optional[torch.Tensor] = None,
+                              ptrs=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``encode_batched_int4`` of ``new - prev`` without writing the difference (even tensor offsets; packed
+    byte e/2 holds flat elements e, e+1; an odd tensor's pad is a zero code). Sources as encode_delta_batched."""
+    _require_even_offsets(layout)
+    dev = _delta_device(new, prev)
+    n_tab, p_tab, _keep = _delta_tables(new, prev, layout, dev, ptrs)
+    packed = _dst(packed, (layout.total + 1) // 2, torch.uint8, dev, "packed")
+    scales = _dst(scales, layout.ntensors, torch.float32, dev, "scales", align=4)
+    partials = _dst(partials, layout.nchunks, torch.int32, dev, "partials", align=4)
+    check(_lib.load().adfl_slq_encode_delta_batched_int4_work(
+        n_tab.data_ptr(), p_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        layout.device_work(dev).data_ptr(), _delta_nwork(layout), bits, packed.data_ptr(), scales.data_ptr(),
+        partials.data_ptr(), _stream(dev)))
+    return packed, scales
+
+
 def decode_batched_int4(packed: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, *,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """unpack_4bit + dequantize over a bucket (layout of encode_batched_int4)."""
@@ -679,6 +784,43 @@ def slq_encode_batched_int4_op(flat: torch.Tensor, offsets: torch.Tensor, sizes:
 def _(flat, offsets, sizes, bits):
     return (flat.new_empty(((flat.numel() + 1) // 2,), dtype=torch.uint8),
             flat.new_empty((sizes.numel(),), dtype=torch.float32))
+
+
+@torch.library.custom_op("adfl::slq_encode_delta_batched", mutates_args=())
+def slq_encode_delta_batched_op(new: torch.Tensor, prev: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor,
+                                bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """slq_encode_batched of (new - prev), two flat fp32 buffers in the same caller-placed layout."""
+    lay = layout_for(offsets, sizes)
+    new, prev = new.reshape(-1), prev.reshape(-1)
+    if new.numel() < lay.total or prev.numel() < lay.total:
+        raise ValueError("slq_encode_delta_batched: flat buffer smaller than the layout")
+    q = _filled(new.numel(), torch.int8, new.device, lay)
+    return encode_delta_batched(new, prev, lay, bits, q=q)
+
+
+@slq_encode_delta_batched_op.register_fake
+def _(new, prev, offsets, sizes, bits):
+    return new.new_empty((new.numel(),), dtype=torch.int8), new.new_empty((sizes.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl::slq_encode_delta_batched_int4", mutates_args=())
+def slq_encode_delta_batched_int4_op(new: torch.Tensor, prev: torch.Tensor, offsets: torch.Tensor,
+                                     sizes: torch.Tensor, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """slq_encode_batched_int4 of (new - prev), two flat fp32 buffers in the same even-offset layout."""
+    lay = layout_for(offsets, sizes)
+    new, prev = new.reshape(-1), prev.reshape(-1)
+    if new.numel() < lay.total or prev.numel() < lay.total:
+        raise ValueError("slq_encode_delta_batched_int4: flat buffer smaller than the layout")
+    nbytes = (new.numel() + 1) // 2
+    gap = int(lay.sizes.sum()) != new.numel()
+    packed = (torch.zeros if gap else torch.empty)(nbytes, dtype=torch.uint8, device=new.device)
+    return encode_delta_batched_int4(new, prev, lay, bits, packed=packed)
+
+
+@slq_encode_delta_batched_int4_op.register_fake
+def _(new, prev, offsets, sizes, bits):
+    return (new.new_empty(((new.numel() + 1) // 2,), dtype=torch.uint8),
+            new.new_empty((sizes.numel(),), dtype=torch.float32))
 
 
 @torch.library.custom_op("adfl::slq_decode_batched_int4", mutates_args=())

@@ -31,8 +31,9 @@ extern "C" {
  * were replaced by adfl_torch_norms (adfl_stoch.h); the absmax / quantize kernels took new arguments.
  * Within 2, adfl_torch_norm_short_max() changed meaning: it is the fp16 / fp64 short-tensor bound only (fp32 /
  * bf16: 2^19); size adfl_torch_norms' `kinds` by adfl_torch_norm_short_max_dt(dtype). `kinds` values other than
- * 0..3 are now ADFL_E_ARG, and a tensor that `kinds` does not name gets a NaN norm instead of no write. */
-#define ADFL_SLQ_ABI_VERSION 2
+ * 0..3 are now ADFL_E_ARG, and a tensor that `kinds` does not name gets a NaN norm instead of no write.
+ * 3: adfl_slq_encode_delta_batched, _work, _int4 and _int4_work were added (no existing entry changed). */
+#define ADFL_SLQ_ABI_VERSION 3
 
 enum {
   ADFL_OK = 0,
@@ -231,6 +232,45 @@ int adfl_slq_dequantize_mean_batched_int4(const uint8_t* d_packed, int64_t row_s
 int adfl_slq_dequantize_add_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
                                     const float* d_scales, float* const* d_targets, int32_t ntensors,
                                     int32_t ntargets, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Delta encode — the send side of a CommType.DELTA round: diff_parameters(prev, new)
+ * (Src/ADFL/model.py:350-358: new - prev per tensor) followed by SLQChannel._quantize_params
+ * (Src/ADFL/Channel/quant.py:74-104), as the clients (Src/ADFL/Client/async_sc.py:106-114,318-324) and
+ * QAFeL's server (Src/ADFL/Server/qafel.py:160-161) send it. x = new - prev is one fp32 subtraction per
+ * element, formed in registers and never written; payload and scales are bit-identical to
+ * adfl_slq_encode_batched* of the materialised difference.
+ *   d_new, d_prev  DEVICE arrays of one device pointer per tensor of the chunk table: tensor t's first fp32
+ *                  element, contiguous, sizes as the table. Two flat buckets are d_new[t] = base + offset[t].
+ *                  The sources have NO alignment precondition beyond fp32's own: a block whose sources are
+ *                  16-byte aligned where its payload is takes 16-byte accesses, any other block goes
+ *                  element-wise with the same result. The sources are not modified.
+ *   d_q / d_packed, d_scales, d_partials  as adfl_slq_encode_batched / _int4 (payload base 16-byte aligned,
+ *                  else ADFL_E_ALIGN; int4: every tensor offset even).
+ * Every other argument error is ADFL_E_ARG and launches nothing: a null pointer, nchunks outside
+ * [1, INT32_MAX], bits outside [1, 8] (int4: [1, 4]), nwork outside [0, nchunks].
+ * The _work forms are the one-launch encode for a bucket whose tensors all have at most
+ * ADFL_SLQ_DELTA_RESIDENT_CHUNKS chunks, over the work list of adfl_slq_build_encode_work (nwork == 0: the two
+ * passes). A 1024-thread block has 128 VGPRs per lane for the 64 registers of the difference and the loads of
+ * both sources: the loads go in two stages, each subtracted as it lands (no scratch), so the bound stays at
+ * ADFL_SLQ_RESIDENT_CHUNKS.
+ * A work list entry naming a larger tensor gets a NaN scale and no payload.
+ * ------------------------------------------------------------------------------------------- */
+#define ADFL_SLQ_DELTA_RESIDENT_CHUNKS 8
+int adfl_slq_encode_delta_batched(const float* const* d_new, const float* const* d_prev,
+                                  const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits, int8_t* d_q,
+                                  float* d_scales, uint32_t* d_partials, void* stream);
+int adfl_slq_encode_delta_batched_work(const float* const* d_new, const float* const* d_prev,
+                                       const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                       int64_t nwork, int bits, int8_t* d_q, float* d_scales, uint32_t* d_partials,
+                                       void* stream);
+int adfl_slq_encode_delta_batched_int4(const float* const* d_new, const float* const* d_prev,
+                                       const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits, uint8_t* d_packed,
+                                       float* d_scales, uint32_t* d_partials, void* stream);
+int adfl_slq_encode_delta_batched_int4_work(const float* const* d_new, const float* const* d_prev,
+                                            const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                            int64_t nwork, int bits, uint8_t* d_packed, float* d_scales,
+                                            uint32_t* d_partials, void* stream);
 
 /* Device staging of a state dict as one bucket (the gather / scatter around every bucketed entry above when
  * the dict's tensors live on the device; the reference's per-tensor loop, quant.py:67-94, has one tensor per

@@ -14,6 +14,11 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             the C3 bucket, in-kernel Philox uniforms; algorithmic bytes: QSGD/RQSGD encode 10N (norm pass
             4N + quantize 4N read, 2N levels+signs write), CNAT encode 6N (one pass), every decode 6N;
             plus the reference's ATen op sequence timed on a 2^22-element host sample
+  delta     the send side of a DELTA round on a C3-shaped dict pair (256 x 45,662 fp32 weights + 256 biases):
+            SLQChannel.send_delta(prev, new) against on_client_send(diff_parameters(prev, new)) with the
+            difference taken by torch on the device, in one process, Infinity Cache flushed before every call;
+            the delta encode alone against torch._foreach_sub + gather + encode_batched alone (HIP events);
+            the same for a log-uniform layout (the two-pass form) and, wall time only, for CPU dicts
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -722,14 +727,150 @@ def mode_stoch(args, world, rank, dev):
     return {"mode": "stoch", "n_gpus": world, "steps": args.steps, **res}
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def _delta_same(a, b) -> bool:
+    """Two QuantParameters equal field for field (the parity flag of the delta leg)."""
+    if list(a.params) != list(b.params) or a.size != b.size:
+        return False
+    for n, p in a.params.items():
+        o = b.params[n]
+        if (p.bits, tuple(p.shape), p.dtype, p.q_dtype, p.data.dtype, p.data.shape, p.data.device) != \
+                (o.bits, tuple(o.shape), o.dtype, o.q_dtype, o.data.dtype, o.data.shape, o.data.device):
+            return False
+        if p.scale != o.scale and not (p.scale != p.scale and o.scale != o.scale):
+            return False
+        pd, od = (p.data.int_repr(), o.data.int_repr()) if p.data.is_quantized else (p.data, o.data)
+        if not torch.equal(pd, od):
+            return False
+    return True
+
+
+def _delta_leg(sizes, args, dev, junk, repeats=5):
+    """One layout of the delta leg. Wall medians are per repeat (`repeats` medians of args.steps calls each): the
+    fused route counts as faster when its worst repeat beats the unfused route's best by more than nothing, i.e.
+    the gap exceeds the unfused route's run-to-run spread (max - min of its medians)."""
+    from adfl_amd import _lib, ops
+    from adfl_amd.Channel import SLQChannel
+    lib = _lib.load()
+    sh = torch.cuda.current_stream(dev).cuda_stream
+    g = torch.Generator(device=dev).manual_seed(0)
+    prev, new = {}, {}
+    for i, n in enumerate(sizes):
+        for name, shape in ((f"layer{i:03d}.weight", (1, n)), (f"layer{i:03d}.bias", (64,))):
+            new[name] = torch.randn(shape, device=dev, generator=g) * 1e-2
+            prev[name] = new[name] + torch.randn(shape, device=dev, generator=g) * 1e-5
+    ch = SLQChannel(8)
+
+    def fused(a=prev, b=new):
+        return ch.send_delta(a, b)[0]
+
+    def unfused(a=prev, b=new):
+        with torch.no_grad():
+            diff = {k: b[k] - a[k] for k in a}   # diff_parameters (model.py:350-358), torch on the dict's device
+        return ch.on_client_send(diff)[0]
+
+    def wall(fn, steps):
+        out = []
+        for _ in range(steps):
+            junk.amax()   # read-flush of the Infinity Cache, as the C3 leg's
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return _median(out)
+
+    parity = _delta_same(fused(), unfused())
+    for _ in range(args.warmup):
+        fused(), unfused()
+    f_ms = [wall(fused, args.steps) for _ in range(repeats)]
+    u_ms = [wall(unfused, args.steps) for _ in range(repeats)]
+    spread = max(u_ms) - min(u_ms)
+    res = {"tensors": len(sizes), "elements": int(sum(sizes)), "parity": parity,
+           "send_delta_ms": round(_median(f_ms), 4), "send_delta_ms_repeats": [round(v, 4) for v in f_ms],
+           "unfused_ms": round(_median(u_ms), 4), "unfused_ms_repeats": [round(v, 4) for v in u_ms],
+           "unfused_spread_ms": round(spread, 4),
+           "fused_faster_than_spread": bool(_median(u_ms) - _median(f_ms) > spread)}
+
+    # the kernels alone, HIP events: the delta encode over prebuilt pointer tables against
+    # torch._foreach_sub + bucket gather + encode_batched (the difference, the bucket of it, its encode)
+    names = [k for k in prev if prev[k].ndim > 1]
+    news, prevs = [new[k] for k in names], [prev[k] for k in names]
+    lay = ops.BucketLayout(list(sizes))             # 64-aligned payload, as send_delta's device route
+    lay_c = ops.BucketLayout(list(sizes), align=1)  # the compact bucket _encode_dict stages a device dict in
+    n_tab = torch.tensor([t.data_ptr() for t in news], dtype=torch.int64).to(dev)
+    p_tab = torch.tensor([t.data_ptr() for t in prevs], dtype=torch.int64).to(dev)
+    q = torch.empty(lay.total, dtype=torch.int8, device=dev)
+    x = torch.empty(lay_c.total, dtype=torch.float32, device=dev)
+    scales = torch.empty(lay.ntensors, device=dev)
+    partials = torch.empty(lay.nchunks, dtype=torch.int32, device=dev)
+    nwork = lay.nwork if lay.max_tensor_chunks <= _lib.DELTA_RESIDENT_CHUNKS else 0
+    chunks, work = lay.device_chunks(dev), lay.device_work(dev)
+
+    def k_fused(ev):
+        junk.amax()
+        if ev is not None:
+            ev[0].record()
+        _lib.check(lib.adfl_slq_encode_delta_batched_work(n_tab.data_ptr(), p_tab.data_ptr(), chunks.data_ptr(),
+                                                          lay.nchunks, work.data_ptr(), nwork, 8, q.data_ptr(),
+                                                          scales.data_ptr(), partials.data_ptr(), sh))
+        if ev is not None:
+            ev[1].record()
+
+    def k_unfused(ev):
+        junk.amax()
+        if ev is not None:
+            ev[0].record()
+        d = torch._foreach_sub(news, prevs)
+        ops.bucket_gather(d, lay_c, x, checked=False)
+        ops.encode_batched(x, lay_c, 8, q=q, scales=scales, partials=partials)
+        if ev is not None:
+            ev[1].record()
+
+    _, evs = timed(k_fused, args.steps, args.warmup, 1, 2)
+    kf = _median([e[0].elapsed_time(e[1]) for e in evs])
+    _, evs = timed(k_unfused, args.steps, args.warmup, 1, 2)
+    ku = _median([e[0].elapsed_time(e[1]) for e in evs])
+    n = int(sum(sizes))
+    res.update({"encode_form": "resident" if nwork else "twopass",
+                "delta_encode_alone_ms": round(kf, 4), "foreach_sub_gather_encode_alone_ms": round(ku, 4),
+                # bytes the delta encode must move: read new + prev (twice in the two passes), write the payload
+                "delta_encode_frac_moved": round((9 if nwork else 17) * n / (kf * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
+
+    # CPU dicts: two H2D copies against a host difference and one H2D (reported, no criterion)
+    prev_h, new_h = {k: v.cpu() for k, v in prev.items()}, {k: v.cpu() for k, v in new.items()}
+    steps = max(3, min(args.steps, 7))
+    res["cpu_dict_parity"] = _delta_same(fused(prev_h, new_h), unfused(prev_h, new_h))
+    res["cpu_dict_send_delta_ms"] = round(wall(lambda: fused(prev_h, new_h), steps), 4)
+    res["cpu_dict_unfused_ms"] = round(wall(lambda: unfused(prev_h, new_h), steps), 4)
+    return res
+
+
+def mode_delta(args, world, rank, dev):
+    """The send side of a DELTA round (FedBuff, FADAS, QAFeL, the simple delta modes): fused against unfused."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    eq = _delta_leg(recipes.bucket_sizes("equal"), args, dev, junk)
+    log = _delta_leg(recipes.bucket_sizes("loguniform", 0), args, dev, junk)
+    return {"mode": "delta", "metric": "send_delta on a C3-shaped device dict pair (256 weights + 256 biases), "
+            "Infinity Cache flushed", "unit": "ms", "value": eq["send_delta_ms"], "parity": eq["parity"] and
+            log["parity"] and eq["cpu_dict_parity"] and log["cpu_dict_parity"], "steps": args.steps,
+            "c3_equal": eq, "c3_loguniform": log}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
     p.add_argument("--graph", action="store_true", help="exchange: time PeerExchange.graph replays")
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
-    p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch"],
-                   required=True)
+    p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
+                                      "delta"], required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -745,7 +886,8 @@ def main():
     assert world == args.gpus, (world, args.gpus)
     dev = torch.device("cuda", local)
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
-            "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch}[args.mode](
+            "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
+            "delta": mode_delta}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
