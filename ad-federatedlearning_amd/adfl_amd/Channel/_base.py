@@ -14,7 +14,7 @@ from typing import Dict, List, Tuple
 import numpy as np
 import torch
 
-from .. import _torchhost, sum_order
+from .. import _torchhost, ops, sum_order
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters, get_parameter_info
 from .channel import Channel, IdentityChannel
 
@@ -274,3 +274,57 @@ class _Unidirectional:
 
     def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
         return IdentityChannel(no_compute_time=True).on_client_receive(c_params)
+
+
+def _delta_on_device(prevs: List[torch.Tensor], news: List[torch.Tensor], dev: torch.device):
+    """(new's, prev's data pointers as CPU int64 tensors) when every tensor of both lists is a contiguous
+    4-byte-element tensor on the staging device (fp32: _delta_pairs saw to the dtype) — the pointer-table
+    route — else None. One native call per list (adfl_torchhost.device_ptrs)."""
+    th = _torchhost.get()
+    ok_n, _, n_ptrs = th.device_ptrs(news, dev.index, 4)
+    if not ok_n:
+        return None
+    ok_p, _, p_ptrs = th.device_ptrs(prevs, dev.index, 4)
+    return (n_ptrs, p_ptrs) if ok_p else None
+
+
+def _delta_pairs(params_prev: Parameters, params_new: Parameters, codable=None):
+    """diff_parameters' view of a dict pair (Src/ADFL/model.py:350-358) without the difference of the ndim > 1
+    entries: (names in params_prev's order, {name: new - prev} for the ndim <= 1 entries, and for the others
+    the fp32 (prev, new) tensors to encode), raising what the reference raises on the way: the key-set
+    assertion, torch's error for shapes `new - prev` cannot broadcast, and quantize's errors for an ndim > 1
+    difference that would be empty or not fp32. A pair on two devices takes params_new's (plain torch would
+    refuse it). codable (the stochastic channels): called as codable(name, dtype, shape) for every ndim > 1 pair
+    in place of quantize's two errors — those channels encode fp16 / bf16 / fp64 differences and send an empty
+    one through their zero-norm branch."""
+    assert set(params_prev.keys()) == set(params_new.keys())
+    names = list(params_prev.keys())
+    plain: Dict[str, torch.Tensor] = {}
+    pairs: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+    batch: List[str] = []   # ndim <= 1 pairs of one shape, dtype and device: subtracted together below
+    with torch.no_grad():
+        for n in names:
+            a, b = params_prev[n], params_new[n]
+            if a.shape == b.shape and a.ndim > 1:
+                pairs[n] = (a, b)
+            elif a.shape == b.shape and a.dtype == b.dtype and a.device == b.device:
+                batch.append(n)
+            else:
+                d = b - (a if a.device == b.device else a.to(b.device))
+                if a.shape != b.shape and d.ndim > 1:   # broadcastable, but not one model's two states
+                    raise RuntimeError(f"send_delta: '{n}' has shape {tuple(a.shape)} in params_prev and "
+                                       f"{tuple(b.shape)} in params_new")
+                plain[n] = d
+        if batch:   # torch's own subtraction, each result its own tensor on its own device, a few launches in all
+            plain.update(zip(batch, torch._foreach_sub([params_new[n] for n in batch],
+                                                       [params_prev[n] for n in batch])))
+        f32 = torch.float32
+        for n, (a, b) in pairs.items():   # quant.py:100-103 on the difference: its dtype is torch's promotion
+            dt = a.dtype if a.dtype == b.dtype else torch.result_type(b, a)
+            if codable is not None:
+                codable(n, dt, b.shape)
+            elif dt != f32 or b.numel() == 0:
+                ops.require_quantizable(torch.empty(b.shape, dtype=dt, device="meta"))
+            if a.dtype != dt or b.dtype != dt:   # e.g. fp16 - fp32: torch converts exactly, then subtracts
+                pairs[n] = (a.to(dt), b.to(dt))
+    return names, plain, pairs

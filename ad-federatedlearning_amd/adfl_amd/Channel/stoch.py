@@ -50,7 +50,7 @@ from .. import stoch as sops
 from .._lib import check
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
 from . import _staging as _stg
-from ._base import _CodecChannel, _passthrough_idle, _Unidirectional
+from ._base import _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle, _Unidirectional
 from ._staging import (_PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _ph, _range_copies, _ranges,
                        _rows_from_ptrs, _serialized, _stage_in, _stage_rows, _staging)
 
@@ -227,6 +227,70 @@ def _codec_encode(codec: str, x_dev, lay, bits: int, uniforms, seed: int, levels
                                              exps=levels.view(torch.int8), signs=signs, norms=norms, ws=ws,
                                              torch_norm=torch_norm)
     return lv, sg
+
+
+def _ushift_for(lay, compact) -> np.ndarray:
+    """Per tensor, compact offset - offset in `lay`: with it an element of the aligned bucket draws the uniform
+    of its index in the compact one (adfl_rqsgd_encode_delta_batched's d_ushift). Cached on `lay`."""
+    us = lay.__dict__.get("_ushift_compact")
+    if us is None:
+        us = lay.__dict__["_ushift_compact"] = np.ascontiguousarray(compact.offsets - lay.offsets, dtype=np.int64)
+    return us
+
+
+@_serialized
+def _encode_delta_stoch(prevs: List[torch.Tensor], news: List[torch.Tensor], names: List[str], codec: str, bits: int,
+                        uniforms=None, seed=None, torch_norm: bool = True):
+    """_encode_stoch of news[k] - prevs[k] (fp32, ndim > 1, equal shapes, non-empty) for every k: the same
+    {name: (data, signs, scale, scale_2)}, each entry on its `news` tensor's device, the same draw from torch's
+    CPU generator and — the uniform of an element being that of its index in the compact bucket — the same
+    bytes as encoding the materialised difference, wherever the dicts live.
+
+    Both dicts contiguous on the staging device: the kernels read the tensors through two pointer tables. RQSGD
+    never writes the difference (sops.rqsgd_encode_delta_batched), its planes in a 64-element-aligned bucket so
+    separately allocated tensors take the vector path, the uniforms kept at their compact indices by `ushift`;
+    QSGD / CNAT write it once into the compact "x" bucket (ops.bucket_diff) and run _codec_encode over it as
+    on_client_send does, norm mode included. CPU or mixed dicts: each dict staged as a compact device bucket
+    (two H2D copies, no range pipeline), the same kernels over the two buckets."""
+    st = _staging()
+    dev = st.device
+    sizes = tuple(int(t.numel()) for t in news)
+    compact = st.layout(sizes)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    ptrs = _delta_on_device(prevs, news, dev)
+    lay, ushift = compact, None
+    if ptrs is not None:
+        src_new, src_prev = news, prevs
+        if codec == "rqsgd":
+            lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
+            ushift = _ushift_for(lay, compact)
+    else:
+        src_new = _stage_in(news, compact, st, "x", torch.float32)
+        src_prev = _stage_in(prevs, compact, st, "x_prev", torch.float32)
+    ws = st.buf("stoch_ws", lay.nchunks * 16, torch.uint8)
+    levels, signs = st.buf("s_levels", lay.total, torch.uint8), st.buf("s_signs", lay.total, torch.int8)
+    norms = st.buf("s_norms", lay.ntensors, torch.float32)
+    mins = st.buf("s_mins", lay.ntensors, torch.float32) if codec == "rqsgd" else None
+    if codec == "rqsgd":
+        lv, sg, _, _ = sops.rqsgd_encode_delta_batched(src_new, src_prev, lay, bits, ptrs=ptrs, ushift=ushift,
+                                                       uniforms=uniforms, seed=seed, counter=0, levels=levels,
+                                                       signs=signs, norms=norms, mins=mins, ws=ws)
+    else:
+        x_dev = ops.bucket_diff(src_new, src_prev, lay, ptrs=ptrs,
+                                out=st.buf("x" if ptrs is not None else "x_diff", lay.total, torch.float32))
+        lv, sg = _codec_encode(codec, x_dev, lay, bits, uniforms, seed, levels, signs, norms, mins, ws, torch_norm)
+    nm_host = st.buf("s_norms_host", 2 * lay.ntensors, torch.float32, pinned=True)
+    nm_host[:lay.ntensors].copy_(norms, non_blocking=True)
+    if mins is not None:
+        nm_host[lay.ntensors:].copy_(mins, non_blocking=True)
+
+    def norms_list():
+        torch.cuda.current_stream(dev).synchronize()
+        return nm_host.tolist()
+    datas, sgs, nm = _hand_out_planes(lv, sg, lay, news, [not t.is_cuda for t in news], st, norms_list,
+                                      native_like=True)
+    return _payloads(names, datas, sgs, nm, lay.ntensors, codec)
 
 
 def _range_encode_args(sub, dev) -> Tuple[int, int, int, int, int, int]:
@@ -745,6 +809,84 @@ class _StochChannel(_CodecChannel):
                 and d.element_size() == 1 and not d.is_quantized and not d.is_floating_point()
                 and g.numel() == d.numel() and g.element_size() == 1 and not g.is_floating_point()
                 and d.is_cuda == g.is_cuda)
+
+    def send_delta(self, params_prev: Parameters, params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``on_client_send(diff_parameters(params_prev, params_new))`` — what every CommType.DELTA strategy sends
+        (the clients, Src/ADFL/Client/async_sc.py:106-114,318-324; QAFeL's server, Src/ADFL/Server/qafel.py:160-161)
+        — without the per-tensor subtractions, difference tensors and gather of the two steps: RQSGD forms the
+        difference of the fp32 ndim > 1 tensors inside its encode kernels and never writes it; QSGD / CNAT write it
+        once, straight into the bucket their encode reads (their scale is the torch-order L2 norm of one flat
+        bucket). Returns (c_params, seconds); c_params equals the two-step result of this channel field for
+        field (data, signs, scale, scale_2, bits, shape, dtype, q_dtype, size), in params_prev's key order
+        (model.py:356), each entry on its params_new tensor's device, and torch's CPU generator is consumed
+        exactly as the two steps consume it — the same draws in the same order, per fp32 bucket and then per
+        dtype group — so one ``torch.manual_seed`` gives one payload by either route, wherever the dicts live.
+        It always encodes, as on_client_send does: the ``U*`` classes' on_server_send is the identity, so a
+        caller that uses send_delta for the server direction of a uni-directional channel sends compressed what
+        the reference sends uncompressed. fp16 / bf16 / fp64 pairs (or pairs promoted to them) are subtracted
+        by torch on their device and encoded in their dtype; ndim <= 1 entries carry torch's ``new - prev`` with
+        scale 0; an empty ndim > 1 pair takes the zero-norm branch. Neither input is modified. Errors: the key-set
+        assertion, torch's for shapes that do not match, the reference's for an ndim > 1 entry that is not
+        floating point."""
+        s_time = time.perf_counter()
+        q_params = self._quantize_delta(params_prev, params_new, self.bits)
+        return q_params, time.perf_counter() - s_time
+
+    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int, uniforms=None,
+                        seed=None) -> QuantParameters:
+        """_quantize_params of the difference (same test hooks: injected uniforms cover the compact fp32 bucket)."""
+        cls = self.__class__.__name__
+
+        def codable(name, dt, shape):   # what _quantize_params raises for the difference tensor
+            _require_codable(name, torch.empty(0, dtype=dt), cls)   # only the dtype matters (a meta tensor words it otherwise)
+
+        names, plain, pairs = _delta_pairs(params_prev, params_new, codable)
+        coded = [n for n, (a, b) in pairs.items() if b.numel() > 0]
+        f32 = [n for n in coded if pairs[n][1].dtype == torch.float32]
+        if uniforms is not None and {pairs[n][1].dtype for n in coded} - {uniforms.dtype}:
+            raise ValueError(f"{cls}: injected uniforms ({uniforms.dtype}) cover one dtype bucket; this dict also "
+                             f"holds {sorted(str(d) for d in {pairs[n][1].dtype for n in coded})}")
+        tn = reference_norm()
+        encoded = (_encode_delta_stoch([pairs[n][0] for n in f32], [pairs[n][1] for n in f32], f32, self.CODEC, bits,
+                                       uniforms if uniforms is None or uniforms.dtype == torch.float32 else None,
+                                       seed, tn) if f32 else {})
+        diffs: Dict[str, torch.Tensor] = {}
+
+        def sub(group):   # torch's own new - prev on the pair's device (params_new's, for a pair on two)
+            with torch.no_grad():
+                news = [pairs[n][1] for n in group]
+                prevs = [a if a.device == b.device else a.to(b.device) for a, b in (pairs[n] for n in group)]
+                diffs.update(zip(group, torch._foreach_sub(news, prevs)))
+
+        if len(f32) < len(coded):
+            for dtype in sops.DT_DTYPES:   # fp16 / bf16 / fp64: one bucket per dtype, in that dtype's arithmetic
+                group = [n for n in coded if pairs[n][1].dtype == dtype]
+                if group:
+                    sub(group)
+                    encoded.update(_encode_stoch_dt(diffs, group, self.CODEC, bits, uniforms, seed, tn))
+        empty = [n for n in pairs if n not in encoded]
+        if empty:
+            sub(empty)
+        qp = QuantParameter
+        pass_signs = torch.zeros(1, dtype=torch.uint8)  # passthrough entries' unused signs, one per call
+        out: Dict[str, QuantParameter] = {}
+        size = 0
+        for n in names:
+            e = encoded.get(n)
+            if e is not None:
+                data, signs, scale, scale_2 = e
+                b = pairs[n][1]
+                out[n] = qp(data, bits, scale, signs, b.shape, b.dtype, data.dtype, scale_2)
+            elif n in pairs:   # empty: vector_norm is 0 -> zero branch
+                d = diffs[n]
+                data = torch.zeros_like(d, dtype=torch.uint8)
+                out[n] = qp(data, bits, torch.tensor(0.0, dtype=d.dtype), torch.ones_like(d, dtype=torch.int8),
+                            d.shape, d.dtype, data.dtype, 0)
+            else:
+                t = plain[n]
+                out[n] = qp(t, bits, 0, pass_signs, t.shape, t.dtype, t.dtype, 0)
+            size += out[n].data.nbytes   # one byte per encoded element
+        return QuantParameters(out, size)
 
     def _quantize_params(self, params: Parameters, bits: int, uniforms=None, seed=None) -> QuantParameters:
         """Biases and running metrics (ndim <= 1) are not quantized."""

@@ -8,11 +8,12 @@ SRC_ROOT = os.path.dirname(PKG_DIR)                      # ad-federatedlearning_
 REPO_ROOT = os.path.dirname(SRC_ROOT)
 CSRC = os.path.join(SRC_ROOT, "csrc", "slq_codec.hip")
 SOURCES = [CSRC, os.path.join(SRC_ROOT, "csrc", "slq_delta.hip"),
-           os.path.join(SRC_ROOT, "csrc", "stoch_codec.hip"), os.path.join(SRC_ROOT, "csrc", "stoch_dtype.hip"),
+           os.path.join(SRC_ROOT, "csrc", "stoch_codec.hip"), os.path.join(SRC_ROOT, "csrc", "stoch_delta.hip"),
+           os.path.join(SRC_ROOT, "csrc", "stoch_dtype.hip"),
            os.path.join(SRC_ROOT, "csrc", "torch_norm.hip"), os.path.join(SRC_ROOT, "csrc", "qerror_ref.hip"),
            os.path.join(SRC_ROOT, "csrc", "bucket_copy.hip"), os.path.join(SRC_ROOT, "csrc", "host_stage.hip"),
            os.path.join(SRC_ROOT, "csrc", "host_copy.cpp")]
-DEPENDS = SOURCES + [os.path.join(SRC_ROOT, "csrc", h) for h in ("slq_device.h", "cnat_log2_table.h", "cnat_log2_dt_table.h", "philox.h", "torch_sum_order.h", "torch_norm_walk.h")]
+DEPENDS = SOURCES + [os.path.join(SRC_ROOT, "csrc", h) for h in ("slq_device.h", "stoch_device.h", "cnat_log2_table.h", "cnat_log2_dt_table.h", "philox.h", "torch_sum_order.h", "torch_norm_walk.h")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libadfl_slq.so")

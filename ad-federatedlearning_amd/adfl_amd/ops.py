@@ -638,6 +638,20 @@ def encode_delta_batched_int4(new, prev, layout: BucketLayout, bits: int = 4, *,
     return packed, scales
 
 
+def bucket_diff(new, prev, layout: BucketLayout, *, out: Optional[torch.Tensor] = None, ptrs=None) -> torch.Tensor:
+    """``new - prev`` of every tensor as one flat fp32 bucket in `layout`, one launch (adfl_bucket_diff): torch's
+    own subtraction bit for bit, written once — the stochastic DELTA route of the codecs whose scale is the
+    torch-order L2 norm (QSGD, CNAT), which encode the bucket as they encode any other. Sources as
+    encode_delta_batched takes them (two flat fp32 device buffers in `layout`, or two lists of fp32 device
+    tensors of its sizes; any addresses); positions no tensor owns are left as they are. ptrs: see _delta_tables."""
+    dev = _delta_device(new, prev)
+    n_tab, p_tab, _keep = _delta_tables(new, prev, layout, dev, ptrs)
+    out = _dst(out, layout.total, torch.float32, dev, "out", align=4)
+    check(_lib.load().adfl_bucket_diff(out.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+                                       n_tab.data_ptr(), p_tab.data_ptr(), _stream(dev)))
+    return out
+
+
 def decode_batched_int4(packed: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, *,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """unpack_4bit + dequantize over a bucket (layout of encode_batched_int4)."""

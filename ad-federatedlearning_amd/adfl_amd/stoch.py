@@ -19,6 +19,7 @@ Randomness: pass ``uniforms`` (fp32 plane indexed like x, values in [0, 1)) to i
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -28,7 +29,7 @@ from .ops import BucketLayout, _dev, _stream
 
 __all__ = ["RngStream", "norms_batched", "qsgd_quantize_batched", "qsgd_encode_batched", "rqsgd_encode_batched",
            "qsgd_decode_batched", "rqsgd_decode_batched", "cnat_encode_batched", "cnat_decode_batched",
-           "philox_uniforms", "workspace", "torch_norms", "NORM_L2", "NORM_LINF", "NORM_L2_TORCH", "DT_DTYPES", "encode_batched_dt",
+           "philox_uniforms", "workspace", "rqsgd_encode_delta_batched", "torch_norms", "NORM_L2", "NORM_LINF", "NORM_L2_TORCH", "DT_DTYPES", "encode_batched_dt",
            "quantize_batched_dt", "norms_batched_dt", "philox_uniforms_dt", "dequantize_mean_batched"]
 
 
@@ -225,6 +226,73 @@ def rqsgd_encode_batched(flat: torch.Tensor, layout: BucketLayout, bits: int, *,
                                                      _uniforms(uniforms, layout), seed, counter, ws.data_ptr(),
                                                      ws.numel(), levels.data_ptr(), signs.data_ptr(),
                                                      norms.data_ptr(), mins.data_ptr(), _stream(dev)))
+    return levels, signs, norms, mins
+
+
+def _delta_f32(src, what: str) -> None:
+    for x in ([src] if isinstance(src, torch.Tensor) else list(src)):
+        if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
+            raise ValueError(f"adfl_amd.stoch: the two-source encode takes fp32 sources, `{what}` holds {x.dtype}")
+
+
+def _ushift(ushift, layout: BucketLayout, dev):
+    """The per-tensor uniform-index shifts as (device int64 tensor or None: no shift, host array or 0), after the check the C ABI
+    cannot make: every tensor's first uniform index, offset + shift, must be >= 0."""
+    if ushift is None:
+        return None, 0
+    us = np.ascontiguousarray(ushift.cpu().numpy() if isinstance(ushift, torch.Tensor) else ushift, dtype=np.int64)
+    cache = layout.__dict__.setdefault("_ushift_dev", {})   # the last shifts used with this layout, already checked
+    key = (us.tobytes(), dev.index)
+    if key not in cache:
+        if us.shape != (layout.ntensors,):
+            raise ValueError(f"adfl_amd.stoch: ushift must hold one int64 per tensor ({layout.ntensors}), got {us.shape}")
+        if ((layout.offsets + us) < 0).any():
+            raise ValueError("adfl_amd.stoch: ushift puts a tensor's first uniform index below 0")
+        cache.clear()
+        cache[key] = torch.from_numpy(us).to(dev)
+    return cache[key], us
+
+
+def rqsgd_encode_delta_batched(new, prev, layout: BucketLayout, bits: int, *, ptrs=None, ushift=None,
+                               uniforms: Optional[torch.Tensor] = None, seed: int = 0, counter: int = 0,
+                               levels: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None,
+                               norms: Optional[torch.Tensor] = None, mins: Optional[torch.Tensor] = None,
+                               ws: Optional[torch.Tensor] = None, resident: Optional[bool] = None):
+    """``rqsgd_encode_batched`` of ``new - prev`` without writing the difference (adfl_rqsgd_encode_delta_batched_work):
+    (levels u8, signs i8, max|x| norms f32, min|x| factors f32) in `layout`, bit-identical to the two steps.
+    `new` / `prev`: two flat fp32 device buffers in `layout`, or two lists of fp32 device tensors of its sizes
+    (validated as ops.encode_delta_batched validates them; any addresses). ushift: per tensor, the element at
+    layout index g draws uniform g + ushift[t] (the Philox word, or uniforms[g + ushift[t]]) — with the planes
+    in a 64-aligned layout and ushift = compact offset - aligned offset the payload is the compact layout's.
+    Injected `uniforms` cover the indices the shifted elements use. resident: as for the other encodes (None =
+    the one-launch form whenever every tensor of the layout fits a block, False = always the two passes; the
+    same bytes).
+    ptrs: see ops._delta_tables."""
+    from .ops import _delta_device, _delta_nwork, _delta_tables
+    if ptrs is None:   # a caller that passes `ptrs` has checked its lists (the channel: fp32 by _delta_pairs)
+        _delta_f32(new, "new")
+        _delta_f32(prev, "prev")
+    dev = _delta_device(new, prev)
+    n_tab, p_tab, _keep = _delta_tables(new, prev, layout, dev, ptrs)
+    us, us_host = _ushift(ushift, layout, dev)
+    if uniforms is not None:
+        top = int((layout.offsets + layout.sizes + us_host).max())
+        if uniforms.dtype != torch.float32 or uniforms.numel() < top:
+            raise ValueError("adfl_amd.stoch: uniforms must be an fp32 plane covering the shifted layout")
+        if not uniforms.is_cuda or not uniforms.is_contiguous() or uniforms.data_ptr() % 16:
+            raise ValueError("adfl_amd.stoch: uniforms must be a contiguous, 16-byte aligned device tensor")
+    levels, signs = _planes(layout, dev, levels, signs, torch.uint8)
+    norms = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if norms is None else norms
+    mins = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if mins is None else mins
+    ws = _ws(ws, layout, dev)
+    # the work list is the resident encodes' (ADFL_SLQ_RESIDENT_CHUNKS); the delta kernel takes tensors up to
+    # ADFL_SLQ_DELTA_RESIDENT_CHUNKS, so a layout beyond that bound runs the two passes (ops._delta_nwork's guard)
+    work = _work(layout, dev, resident) if _delta_nwork(layout) else (0, 0)
+    check(_lib.load().adfl_rqsgd_encode_delta_batched_work(
+        n_tab.data_ptr(), p_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        *work, bits, uniforms.data_ptr() if uniforms is not None else None,
+        us.data_ptr() if us is not None else None, seed, counter, ws.data_ptr(), ws.numel(), levels.data_ptr(),
+        signs.data_ptr(), norms.data_ptr(), mins.data_ptr(), _stream(dev)))
     return levels, signs, norms, mins
 
 
@@ -428,14 +496,9 @@ def _check_codec(codec: str) -> None:
         raise ValueError(f"adfl stochastic ops: codec must be one of {sorted(_CODEC_IDS)}, got {codec!r}")
 
 
-@torch.library.custom_op("adfl::stoch_encode_batched", mutates_args=())
-def stoch_encode_batched_op(flat: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int,
-                            seed: int, counter: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(levels — uint8, CNAT: int8 exponents —, signs int8, norms f32, mins f32 — RQSGD's min|x|, else 0) of
-    a flat buffer; uniforms from the Philox stream (seed, counter). fp32 buffers take the fp32 kernels;
-    fp16 / bf16 / fp64 ones are encoded in their own dtype's arithmetic, as the reference computes them
-    (encode_batched_dt), and their norms / mins come back as the fp32 values the decode multiplies by (the
-    channels' Python-float norm as an fp32 scalar; exact for fp16 / bf16 norms)."""
+def _stoch_encode_flat(flat: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int,
+                       seed: int, counter: int):
+    """stoch_encode_batched's body (stoch_encode_delta_batched runs it over the difference bucket)."""
     from .ops import _filled, layout_for
     _check_codec(codec)
     lay = layout_for(offsets, sizes)
@@ -459,12 +522,55 @@ def stoch_encode_batched_op(flat: torch.Tensor, offsets: torch.Tensor, sizes: to
     return lv, sg, nr, mins
 
 
+@torch.library.custom_op("adfl::stoch_encode_batched", mutates_args=())
+def stoch_encode_batched_op(flat: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int,
+                            seed: int, counter: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(levels — uint8, CNAT: int8 exponents —, signs int8, norms f32, mins f32 — RQSGD's min|x|, else 0) of
+    a flat buffer; uniforms from the Philox stream (seed, counter). fp32 buffers take the fp32 kernels;
+    fp16 / bf16 / fp64 ones are encoded in their own dtype's arithmetic, as the reference computes them
+    (encode_batched_dt), and their norms / mins come back as the fp32 values the decode multiplies by (the
+    channels' Python-float norm as an fp32 scalar; exact for fp16 / bf16 norms)."""
+    return _stoch_encode_flat(flat, offsets, sizes, codec, bits, seed, counter)
+
+
 @stoch_encode_batched_op.register_fake
 def _(flat, offsets, sizes, codec, bits, seed, counter):
     n, t = flat.numel(), sizes.numel()
     return (flat.new_empty((n,), dtype=torch.int8 if codec == "cnat" else torch.uint8),
             flat.new_empty((n,), dtype=torch.int8), flat.new_empty((t,), dtype=torch.float32),
             flat.new_empty((t,), dtype=torch.float32))
+
+
+@torch.library.custom_op("adfl::stoch_encode_delta_batched", mutates_args=())
+def stoch_encode_delta_batched_op(new: torch.Tensor, prev: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor,
+                                  codec: str, bits: int, seed: int,
+                                  counter: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """stoch_encode_batched of (new - prev), two flat fp32 buffers in the same caller-placed layout. rqsgd: the
+    two-source kernels (the difference is never written); qsgd / cnat: one bucket_diff launch, then exactly what
+    stoch_encode_batched runs over it, its norm mode included."""
+    from .ops import _filled, bucket_diff, layout_for
+    _check_codec(codec)
+    if new.dtype != torch.float32 or prev.dtype != torch.float32:
+        raise ValueError(f"stoch_encode_delta_batched: fp32 buffers only, got {new.dtype} / {prev.dtype}")
+    lay = layout_for(offsets, sizes)
+    new, prev = new.reshape(-1), prev.reshape(-1)
+    if new.numel() < lay.total or prev.numel() < lay.total:
+        raise ValueError("stoch_encode_delta_batched: flat buffer smaller than the layout")
+    dev = new.device
+    if codec != "rqsgd":
+        diff = bucket_diff(new, prev, lay, out=torch.empty(new.numel(), dtype=torch.float32, device=dev))
+        return _stoch_encode_flat(diff, offsets, sizes, codec, bits, seed, counter)
+    lv = _filled(new.numel(), torch.uint8, dev, lay)
+    sg = _filled(new.numel(), torch.int8, dev, lay)
+    return rqsgd_encode_delta_batched(new, prev, lay, bits, seed=seed, counter=counter, levels=lv, signs=sg)
+
+
+@stoch_encode_delta_batched_op.register_fake
+def _(new, prev, offsets, sizes, codec, bits, seed, counter):
+    n, t = new.numel(), sizes.numel()
+    return (new.new_empty((n,), dtype=torch.int8 if codec == "cnat" else torch.uint8),
+            new.new_empty((n,), dtype=torch.int8), new.new_empty((t,), dtype=torch.float32),
+            new.new_empty((t,), dtype=torch.float32))
 
 
 @torch.library.custom_op("adfl::stoch_decode_batched", mutates_args=())

@@ -9,6 +9,10 @@
 // ptrs[tensor] + (start - the tensor's first element), 16-byte words when source and destination share
 // their phase mod 16 (bytes up to the first boundary and after the last), 4-byte words when they share it
 // mod 4, bytes otherwise. Pads between tensors in an aligned bucket are in no chunk: never read or written.
+// adfl_bucket_diff is the same walk with two sources: the bucket receives new - prev (fp32).
+// Two conventions for an empty table sit in this file: adfl_bucket_gather / adfl_bucket_scatter accept nchunks == 0
+// and do nothing (a dict with nothing to stage), adfl_bucket_diff follows the delta encode entries of
+// adfl_slq.h / adfl_stoch.h, for which a chunk count outside [1, INT32_MAX] is ADFL_E_ARG.
 
 #include <hip/hip_runtime.h>
 
@@ -16,6 +20,7 @@
 
 #include "adfl_host.h"
 #include "adfl_slq.h"
+#include "adfl_stoch.h"
 
 namespace {
 
@@ -62,6 +67,50 @@ __global__ __launch_bounds__(kBlock) void k_bucket_copy(uint8_t* __restrict__ bu
     copy_words<uint8_t>(dst, src, n);
 }
 
+// The difference of two dicts as one flat fp32 bucket (adfl_bucket_diff): out[c.start + i] = new_t[i] - prev_t[i],
+// one fp32 subtraction per element (torch's `new - prev`), 8 bytes read and 4 written per element. The word
+// size is k_bucket_copy's decision taken from three addresses: 16-byte words when the bucket slot and both
+// sources share their phase mod 16 (all of the chunk's loads of both sources in flight before the first
+// subtraction; elements up to the first boundary and after the last one by one), 4-byte words otherwise.
+// Sources are read non-temporally (dead after the read); the stores allocate (the norm and encode read them).
+__global__ __launch_bounds__(kBlock) void k_bucket_diff(float* __restrict__ out,
+                                                        const adfl_slq_chunk* __restrict__ chunks,
+                                                        const float* const* __restrict__ nws,
+                                                        const float* const* __restrict__ pvs) {
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const int64_t off = c.start - chunks[c.first_chunk].start;
+  float* o = out + c.start;
+  const float* a = nws[c.tensor] + off;
+  const float* b = pvs[c.tensor] + off;
+  const int n = c.len;
+  const int tid = (int)threadIdx.x;
+  const uintptr_t phase = ((uintptr_t)o ^ (uintptr_t)a) | ((uintptr_t)o ^ (uintptr_t)b);  // block-uniform
+  if ((phase & 15) != 0) {
+    for (int i = tid; i < n; i += kBlock) o[i] = __builtin_nontemporal_load(a + i) - __builtin_nontemporal_load(b + i);
+    return;
+  }
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  constexpr int kPer = ADFL_SLQ_CHUNK_ELEMS / 4 / kBlock;  // 8 float4 per thread and source
+  const int h = (int)(((16u - ((uintptr_t)o & 15u)) & 15u) >> 2);
+  const int head = h < n ? h : n;
+  const int n4 = (n - head) >> 2;
+  const f4v* a4 = reinterpret_cast<const f4v*>(a + head);
+  const f4v* b4 = reinterpret_cast<const f4v*>(b + head);
+  f4v* o4 = reinterpret_cast<f4v*>(o + head);
+  const f4v zero = {0.f, 0.f, 0.f, 0.f};
+  f4v va[kPer], vb[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) va[j] = tid + j * kBlock < n4 ? __builtin_nontemporal_load(a4 + tid + j * kBlock) : zero;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) vb[j] = tid + j * kBlock < n4 ? __builtin_nontemporal_load(b4 + tid + j * kBlock) : zero;
+  const int tail = head + (n4 << 2);
+  const int e = tid < head ? tid : (tid - head < n - tail ? tail + tid - head : -1);  // the < 4 + < 4 edge elements
+  if (e >= 0) o[e] = __builtin_nontemporal_load(a + e) - __builtin_nontemporal_load(b + e);
+#pragma unroll
+  for (int j = 0; j < kPer; ++j)
+    if (tid + j * kBlock < n4) o4[tid + j * kBlock] = va[j] - vb[j];
+}
+
 int launch(bool to_bucket, void* d_bucket, const adfl_slq_chunk* d_chunks, int64_t nchunks, const void* d_ptrs,
            int32_t elem_bytes, void* stream) {
   if (!d_bucket || !d_chunks || !d_ptrs || nchunks < 0 || nchunks > INT32_MAX) return ADFL_E_ARG;
@@ -97,6 +146,15 @@ int adfl_bucket_gather(void* d_bucket, const adfl_slq_chunk* d_chunks, int64_t n
 int adfl_bucket_scatter(const void* d_bucket, const adfl_slq_chunk* d_chunks, int64_t nchunks, void* const* d_dsts,
                         int32_t elem_bytes, void* stream) {
   return launch(false, const_cast<void*>(d_bucket), d_chunks, nchunks, d_dsts, elem_bytes, stream);
+}
+
+int adfl_bucket_diff(float* d_out, const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* const* d_new,
+                     const float* const* d_prev, void* stream) {
+  if (!d_out || !d_chunks || !d_new || !d_prev || nchunks < 1 || nchunks > INT32_MAX) return ADFL_E_ARG;
+  hipLaunchKernelGGL(k_bucket_diff, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_out, d_chunks,
+                     d_new, d_prev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ADFL_OK : (int)e;
 }
 
 }  // extern "C"

@@ -167,6 +167,56 @@ int adfl_cnat_encode_batched_work(const float* d_x, const adfl_slq_chunk* d_chun
                                   uint64_t seed, uint64_t counter, void* d_workspace, int64_t workspace_bytes,
                                   int8_t* d_exps, int8_t* d_signs, float* d_norms, void* stream);
 
+/* ---- DELTA rounds: the encode of new - prev (diff_parameters, Src/ADFL/model.py:350-358, then the codec) ----
+ * Sources as adfl_slq_encode_delta_batched addresses them: d_new / d_prev are device arrays of one fp32 pointer
+ * per tensor, read through the chunk table as ptrs[c.tensor] + (c.start - t0), t0 the tensor's offset in the
+ * chunk table (where its planes start). No precondition on the source addresses (no ADFL_E_ALIGN for them):
+ * a block whose two source addresses are 16-byte aligned where its planes reach a 4-byte boundary works in
+ * 4-element groups, any other element by element with the same results. The plane bases are 16-byte aligned.
+ *
+ * RQSGD (max|x| and min|x| are order-free, so the difference is never written): two passes over both sources
+ * and a per-tensor finalize, three launches, 18 bytes per element (any layout), or one launch (below).
+ *   d_ushift: per tensor (int64, device), or NULL meaning 0. The element at chunk-table index g of tensor t uses
+ *             uniform index g + d_ushift[t]: Philox word (g + ushift) % 4 of block counter + (g + ushift) / 4, or
+ *             d_uniforms[g + ushift] when uniforms are injected. It decouples the draw from the plane address: a
+ *             caller that keeps the planes in a 64-element-aligned layout passes compact_offset[t] -
+ *             aligned_offset[t] and gets the compact layout's payload. g + ushift must be >= 0 for every
+ *             tensor's first element; the library cannot see device memory, so the caller checks it
+ *             (adfl_amd.stoch raises ValueError). Tensors with ushift % 4 == 0 draw one Philox block per four
+ *             elements; the others draw from two (a lane takes the second from the next lane).
+ *   Contract: d_levels, d_signs, d_norms and d_mins equal adfl_rqsgd_encode_batched_work's over a bucket that
+ *             holds fl(new - prev) with tensor t at offset t0 + ushift[t], with the same bits / seed / counter /
+ *             uniforms, bit for bit — the norm == 0 fill (levels 0, signs 1) and the NaN norm / min included.
+ *   Errors, nothing launched: ADFL_E_ARG (a null table, plane, norms, mins or workspace; nchunks outside
+ *             [1, INT32_MAX]; a null work list or nwork outside [0, nchunks]), ADFL_E_BITS, ADFL_E_WORKSPACE
+ *             (fewer than adfl_stoch_workspace_bytes(nchunks) bytes), ADFL_E_ALIGN (workspace, plane or uniform base).
+ * The _work entry is the one-launch form for a bucket whose tensors ALL have at most
+ * ADFL_SLQ_DELTA_RESIDENT_CHUNKS chunks, over the work list of adfl_slq_build_encode_work (nwork == 0: the
+ * two-pass entry): a 1024-thread block holds one whole tensor's difference in registers between its max / min
+ * reduction and the quantize, so both sources are read once (10 bytes per element) and the workspace is not
+ * used (it is still checked). Same outputs bit for bit. A work list entry naming a larger tensor gets a NaN norm
+ * and min and no payload. */
+int adfl_rqsgd_encode_delta_batched(const float* const* d_new, const float* const* d_prev,
+                                    const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                    const float* d_uniforms, const int64_t* d_ushift, uint64_t seed, uint64_t counter,
+                                    void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels, int8_t* d_signs,
+                                    float* d_norms, float* d_mins, void* stream);
+int adfl_rqsgd_encode_delta_batched_work(const float* const* d_new, const float* const* d_prev,
+                                         const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                         int64_t nwork, int bits, const float* d_uniforms, const int64_t* d_ushift,
+                                         uint64_t seed, uint64_t counter, void* d_workspace, int64_t workspace_bytes,
+                                         uint8_t* d_levels, int8_t* d_signs, float* d_norms, float* d_mins,
+                                         void* stream);
+
+/* QSGD / CNAT scale by the torch-order L2 norm, which reads one flat bucket: their DELTA route writes the
+ * difference once and runs the entries above over it. d_out[c.start + i] = new_t[i] - prev_t[i] for every
+ * chunk (one launch, 8 bytes read and 4 written per element; bytes outside every chunk untouched), equal to
+ * torch's `new - prev` bit for bit (NaN by position, not payload). Any alignment: 16-byte words when the slot
+ * and both sources share their phase mod 16, 4-byte words otherwise. ADFL_E_ARG for a null pointer or nchunks
+ * outside [1, INT32_MAX]. */
+int adfl_bucket_diff(float* d_out, const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* const* d_new,
+                     const float* const* d_prev, void* stream);
+
 /* The Philox uniforms the codecs draw: d_out[i] = u(start + i) of stream (seed, counter), i < n.
  * (Exposed for tests and for callers that want the uniforms a call used.) */
 int adfl_philox_uniforms(float* d_out, int64_t n, int64_t start, uint64_t seed, uint64_t counter, void* stream);

@@ -19,6 +19,8 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             difference taken by torch on the device, in one process, Infinity Cache flushed before every call;
             the delta encode alone against torch._foreach_sub + gather + encode_batched alone (HIP events);
             the same for a log-uniform layout (the two-pass form) and, wall time only, for CPU dicts
+  delta_stoch  the same protocol for QSGDChannel / RQSGDChannel / CNATChannel(8).send_delta, and in HIP events the
+            two-source RQSGD encode and bucket_diff against torch._foreach_sub + gather (+ rqsgd_encode_batched)
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -863,6 +865,150 @@ def mode_delta(args, world, rank, dev):
             "c3_equal": eq, "c3_loguniform": log}
 
 
+def _stoch_same(a, b) -> bool:
+    """Two stochastic QuantParameters equal field for field (the parity flag of the delta_stoch leg)."""
+    def same_scale(x, y):
+        if isinstance(x, torch.Tensor) or isinstance(y, torch.Tensor):
+            return isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.dtype == y.dtype and torch.equal(x, y)
+        return type(x) is type(y) and (x == y or (x != x and y != y))
+    if list(a.params) != list(b.params) or a.size != b.size:
+        return False
+    for n, p in a.params.items():
+        o = b.params[n]
+        if (p.bits, tuple(p.shape), p.dtype, p.q_dtype) != (o.bits, tuple(o.shape), o.dtype, o.q_dtype):
+            return False
+        if not (same_scale(p.scale, o.scale) and same_scale(p.scale_2, o.scale_2)):
+            return False
+        for x, y in ((p.data, o.data), (p.signs, o.signs)):
+            if (x.dtype, x.shape, x.device) != (y.dtype, y.shape, y.device) or not torch.equal(x, y):
+                return False
+    return True
+
+
+def _delta_stoch_leg(sizes, args, dev, junk, repeats=5):
+    """One layout of the delta_stoch leg, _delta_leg's protocol per stochastic codec: send_delta against
+    on_client_send of torch's difference on the device (a route this library has not changed), both under one
+    torch.manual_seed for the parity flag; then the kernels alone in HIP events."""
+    from adfl_amd import ops, stoch
+    from adfl_amd.Channel import CNATChannel, QSGDChannel, RQSGDChannel
+    g = torch.Generator(device=dev).manual_seed(0)
+    prev, new = {}, {}
+    for i, n in enumerate(sizes):
+        for name, shape in ((f"layer{i:03d}.weight", (1, n)), (f"layer{i:03d}.bias", (64,))):
+            new[name] = torch.randn(shape, device=dev, generator=g) * 1e-2
+            prev[name] = new[name] + torch.randn(shape, device=dev, generator=g) * 1e-5
+    prev_h, new_h = {k: v.cpu() for k, v in prev.items()}, {k: v.cpu() for k, v in new.items()}
+
+    def wall(fn, steps):
+        out = []
+        for _ in range(steps):
+            junk.amax()   # read-flush of the Infinity Cache
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return _median(out)
+
+    res = {"tensors": len(sizes), "elements": int(sum(sizes))}
+    for codec, cls in (("qsgd", QSGDChannel), ("rqsgd", RQSGDChannel), ("cnat", CNATChannel)):
+        ch = cls(8)
+
+        def fused(a=prev, b=new):
+            return ch.send_delta(a, b)[0]
+
+        def unfused(a=prev, b=new):
+            with torch.no_grad():
+                diff = {k: b[k] - a[k] for k in a}   # diff_parameters (model.py:350-358), torch on the dict's device
+            return ch.on_client_send(diff)[0]
+
+        def seeded(fn, *a):
+            torch.manual_seed(1234)
+            return fn(*a)
+
+        parity = _stoch_same(seeded(fused), seeded(unfused))
+        for _ in range(args.warmup):
+            fused(), unfused()
+        f_ms = [wall(fused, args.steps) for _ in range(repeats)]
+        u_ms = [wall(unfused, args.steps) for _ in range(repeats)]
+        spread = max(u_ms) - min(u_ms)
+        steps = max(3, min(args.steps, 7))
+        res[codec] = {"parity": parity, "send_delta_ms": round(_median(f_ms), 4),
+                      "send_delta_ms_repeats": [round(v, 4) for v in f_ms], "unfused_ms": round(_median(u_ms), 4),
+                      "unfused_ms_repeats": [round(v, 4) for v in u_ms], "unfused_spread_ms": round(spread, 4),
+                      "fused_faster_than_spread": bool(_median(u_ms) - _median(f_ms) > spread),
+                      # CPU dicts: two H2D copies against a host difference and one H2D (reported, no criterion)
+                      "cpu_dict_parity": _stoch_same(seeded(fused, prev_h, new_h), seeded(unfused, prev_h, new_h)),
+                      "cpu_dict_send_delta_ms": round(wall(lambda: fused(prev_h, new_h), steps), 4),
+                      "cpu_dict_unfused_ms": round(wall(lambda: unfused(prev_h, new_h), steps), 4)}
+
+    # the kernels alone, HIP events
+    names = [k for k in prev if prev[k].ndim > 1]
+    news, prevs = [new[k] for k in names], [prev[k] for k in names]
+    lay = ops.BucketLayout(list(sizes))             # 64-aligned planes, as send_delta's device route
+    lay_c = ops.BucketLayout(list(sizes), align=1)  # the compact bucket of the two-step route
+    ptrs = (torch.tensor([t.data_ptr() for t in news], dtype=torch.int64).to(dev),
+            torch.tensor([t.data_ptr() for t in prevs], dtype=torch.int64).to(dev))   # prebuilt device tables
+    ushift = lay_c.offsets - lay.offsets
+    x = torch.empty(lay_c.total, dtype=torch.float32, device=dev)
+    bufs = {k: torch.empty(lay.total, dtype=dt, device=dev) for k, dt in (("levels", torch.uint8), ("signs", torch.int8))}
+    nm = {k: torch.empty(lay.ntensors, device=dev) for k in ("norms", "mins")}
+    ws = stoch.workspace(lay, dev)
+
+    def event_ms(body):
+        def run(ev):
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            body()
+            if ev is not None:
+                ev[1].record()
+        _, evs = timed(run, args.steps, args.warmup, 1, 2)
+        return round(_median([e[0].elapsed_time(e[1]) for e in evs]), 4)
+
+    def sub_gather():
+        ops.bucket_gather(torch._foreach_sub(news, prevs), lay_c, x, checked=False)
+
+    def two_step_rqsgd():
+        sub_gather()
+        stoch.rqsgd_encode_batched(x, lay_c, 8, seed=1, **bufs, **nm, ws=ws)
+
+    n = int(sum(sizes))
+    phases = (ushift % 4 != 0)
+    res["kernels"] = {
+        "rqsgd_delta_encode_ms": event_ms(lambda: stoch.rqsgd_encode_delta_batched(
+            news, prevs, lay, 8, ptrs=ptrs, ushift=ushift, seed=1, **bufs, **nm, ws=ws)),
+        "rqsgd_delta_encode_twopass_ms": event_ms(lambda: stoch.rqsgd_encode_delta_batched(
+            news, prevs, lay, 8, ptrs=ptrs, ushift=ushift, seed=1, **bufs, **nm, ws=ws, resident=False)),
+        # every tensor on the one-block-per-group path: what the straddling tensors cost
+        "rqsgd_delta_encode_ushift0_ms": event_ms(lambda: stoch.rqsgd_encode_delta_batched(
+            news, prevs, lay, 8, ptrs=ptrs, seed=1, **bufs, **nm, ws=ws)),
+        "rqsgd_foreach_sub_gather_encode_ms": event_ms(two_step_rqsgd),
+        "bucket_diff_ms": event_ms(lambda: ops.bucket_diff(news, prevs, lay_c, out=x, ptrs=ptrs)),
+        "foreach_sub_gather_ms": event_ms(sub_gather),
+        "rqsgd_delta_form": "resident" if lay.nwork else "twopass", "tensors_on_the_straddling_path": int(phases.sum()),
+        "rqsgd_delta_frac_moved": None, "bucket_diff_frac_moved": None}
+    k = res["kernels"]
+    k["rqsgd_delta_frac_moved"] = round((10 if lay.nwork else 18) * n / (k["rqsgd_delta_encode_ms"] * 1e-3) / 1e9
+                                        / HBM_PEAK_GBS, 4)
+    k["bucket_diff_frac_moved"] = round(12 * n / (k["bucket_diff_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    return res
+
+
+def mode_delta_stoch(args, world, rank, dev):
+    """The send side of a DELTA round through QSGD / RQSGD / CNAT: send_delta against the two steps."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    eq = _delta_stoch_leg(recipes.bucket_sizes("equal"), args, dev, junk)
+    log = _delta_stoch_leg(recipes.bucket_sizes("loguniform", 0), args, dev, junk)
+    codecs = ("qsgd", "rqsgd", "cnat")
+    return {"mode": "delta_stoch", "metric": "QSGDChannel(8).send_delta on a C3-shaped device dict pair (256 weights "
+            "+ 256 biases), Infinity Cache flushed", "unit": "ms", "value": eq["qsgd"]["send_delta_ms"],
+            "parity": all(leg[c][f] for leg in (eq, log) for c in codecs for f in ("parity", "cpu_dict_parity")),
+            "steps": args.steps, "c3_equal": eq, "c3_loguniform": log}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -870,7 +1016,7 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta"], required=True)
+                                      "delta", "delta_stoch"], required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -887,7 +1033,7 @@ def main():
     dev = torch.device("cuda", local)
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
-            "delta": mode_delta}[args.mode](
+            "delta": mode_delta, "delta_stoch": mode_delta_stoch}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
