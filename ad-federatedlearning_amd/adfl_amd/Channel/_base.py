@@ -1,6 +1,7 @@
 """What the SLQ channels (quant.py) and the stochastic channels (stoch.py) share above the staging layer:
 ``_CodecChannel``, the class skeleton of a bi-directional codec channel (the reference's six-method surface,
-``receive_add_`` and ``receive_mean`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
+``receive_add_``, ``receive_mean`` and the asynchronous server's ``receive_axpby`` / ``receive_scaled`` /
+``receive_scaled_add_`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
 uni-directional variants; and the host aggregate of the entries no device kernel takes (``_aggregate_entries``,
 ``device_mean_order_ok``).
 
@@ -16,6 +17,7 @@ import torch
 
 from .. import _torchhost, ops, sum_order
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters, get_parameter_info
+from ._staging import _hand_out, _serialized, _stage_in, _stage_out, _staging
 from .channel import Channel, IdentityChannel
 
 
@@ -144,7 +146,10 @@ class _CodecChannel(Channel):
       when the updates are anything else (they are then classified entry by entry, with the hooks below);
     * ``_fusable(p)``: an entry the decode-mean launch takes; ``_mean_shape(p)``: its decoded shape (one shape
       across the updates fuses); ``_mean_payloads(all_c_params, names)``: the means of such entries;
-    * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor."""
+    * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor;
+    * ``_apply_payload(c_params, names, st)``: the ``_fusable`` entries' payloads staged on the device and the
+      codec's fused decode + axpby over them — what receive_axpby, receive_scaled and receive_scaled_add_ (the
+      asynchronous server's update step) are written around."""
 
     SIGN_BITS = 0    # sent per weight beside its `bits` (the stochastic codecs' sign plane: 1)
     NORM_BYTES = 4   # sent per quantized tensor: its scale or norm (RQSGD: norm + minimum factor, 8)
@@ -257,12 +262,162 @@ class _CodecChannel(Channel):
             out.update(_aggregate_entries(rest, parts))
         return {n: out[n] for n in names}, time.perf_counter() - s_time
 
+    # -- the asynchronous server's update step: decode + axpby / scale ---------------------------------------
+    def receive_axpby(self, c_params: CompressedParameters, base: Parameters, alpha: float,
+                      beta: float) -> Tuple[Parameters, float]:
+        """``add_parameters(base, self.on_server_receive(c_params)[0], alpha, beta)`` (Src/ADFL/model.py:326-334)
+        — FedAsync's update with (1 - alpha_t, alpha_t) (Src/ADFL/Strategy/fed_async.py:80-81) and Simple
+        DELTA's with (1.0, 1.0) (Strategy/simple.py:100), bit-identical to them: per element
+        fp32(fp32(alpha * base) + fp32(beta * decoded)). Returns (sum, seconds); keys in c_params' order, `base`
+        unmodified, every returned tensor its own storage.
+
+        The entries ``_receive`` decodes on the device whose base tensor is fp32, contiguous and 16-byte aligned
+        (all of them on the staging device, or all on the CPU) are decoded and combined by one launch
+        (``_apply_payload``): no decoded tensor is written. Every other entry takes the reference's route:
+        decode, then ``(alpha * base) + (beta * decoded)``."""
+        assert isinstance(c_params, QuantParameters)
+        assert set(base.keys()) == set(c_params.params.keys())   # add_parameters, model.py:327
+        s_time = time.perf_counter()
+        out: Parameters = {}
+        for where, names in self._apply_groups(c_params, [base]):
+            out.update(zip(names, _apply_fused(self, c_params, names, where, [base], False, alpha, beta)))
+        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in out}, 0)
+        if rest.params:
+            decoded, _ = self.on_server_receive(rest)
+            with torch.no_grad():
+                for n, d in decoded.items():
+                    out[n] = (alpha * base[n]) + (beta * d.to(base[n].device))
+        return {n: out[n] for n in c_params.params}, time.perf_counter() - s_time
+
+    def receive_scaled(self, c_params: CompressedParameters, factor: float) -> Tuple[Parameters, float]:
+        """``self.on_server_receive(c_params)[0]`` after FedBuff's staleness scaling ``for t in D.values():
+        t.float().mul_(factor)`` (Src/ADFL/Strategy/fed_buff.py:72-75) — the update that becomes the buffer: per
+        element fp32(factor * decoded), so a -0.0 stays -0.0. fp32 entries are scaled; ``.float()`` copies every
+        other dtype, which is therefore left as it is, as in the reference. Returns (update, seconds)."""
+        assert isinstance(c_params, QuantParameters)
+        s_time = time.perf_counter()
+        out: Parameters = {}
+        for where, names in self._apply_groups(c_params, None):
+            out.update(zip(names, _apply_fused(self, c_params, names, where, None, False, 1.0, factor)))
+        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in out}, 0)
+        if rest.params:
+            decoded, _ = self.on_server_receive(rest)
+            with torch.no_grad():
+                for t in decoded.values():
+                    t.float().mul_(factor)
+            out.update(decoded)
+        return {n: out[n] for n in c_params.params}, time.perf_counter() - s_time
+
+    def receive_scaled_add_(self, c_params: CompressedParameters, targets: List[Parameters], factor: float) -> float:
+        """For every ``t`` in ``targets``: FedBuff's scaling of the decoded update (receive_scaled) followed by
+        ``add_parameters_inpace(t, decoded, 1, 1, False)`` (Src/ADFL/Strategy/fed_buff.py:72-80) — the later
+        updates of a buffer: per element fp32(t + fp32(factor * decoded)). With factor == 1.0 it equals
+        ``receive_add_``. Returns the seconds spent."""
+        assert isinstance(c_params, QuantParameters)
+        for t in targets:
+            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
+        s_time = time.perf_counter()
+        done = set()
+        if targets:
+            for where, names in self._apply_groups(c_params, targets):
+                _apply_fused(self, c_params, names, where, targets, True, 1.0, factor)
+                done.update(names)
+        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in done}, 0)
+        if rest.params:
+            decoded, _ = self.on_server_receive(rest)
+            with torch.no_grad():
+                for d in decoded.values():
+                    d.float().mul_(factor)
+                for t in targets:
+                    for n, d in decoded.items():
+                        t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
+        return time.perf_counter() - s_time
+
+    def _apply_groups(self, c_params: QuantParameters, models):
+        """The fused entries of receive_axpby / receive_scaled / receive_scaled_add_ as [("cuda" | "cpu", names)]:
+        entries _receive would decode on the device (``_fusable``) whose tensor in every model of `models` is
+        fp32, contiguous, 16-byte aligned, of the decoded shape, and with the others either on the staging device
+        or on the CPU. models None (receive_scaled): grouped by where the payload, hence the decoded tensor,
+        lives."""
+        dev_idx = torch.cuda.current_device() if torch.cuda.is_available() else None
+        groups: Dict[str, List[str]] = {"cuda": [], "cpu": []}
+        if dev_idx is None:
+            return []
+        for n, p in c_params.params.items():
+            if not self._fusable(p):
+                continue
+            shape = torch.Size(self._apply_shape(p))
+            if models is None:
+                ts = [p.data]
+            else:
+                ts = [m[n] for m in models]
+                if not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.shape == shape
+                           and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts):
+                    continue
+            if all(t.is_cuda and t.device.index == dev_idx for t in ts):
+                groups["cuda"].append(n)
+            elif not any(t.is_cuda for t in ts):
+                groups["cpu"].append(n)
+        return [(w, ns) for w, ns in groups.items() if ns]
+
+    def _apply_shape(self, p: QuantParameter):
+        """The decoded shape of a ``_fusable`` entry."""
+        return self._mean_shape(p)
+
+    def _apply_payload(self, c_params: QuantParameters, names: List[str], st):
+        """Stage the payloads of `names` on the device: (element layout, launch), launch(bases, outs, alpha, beta)
+        running the codec's fused decode + axpby over them (ops.dequantize_axpby_batched's bases / outs)."""
+        raise NotImplementedError
+
     @staticmethod
     def _mean_shape(p: QuantParameter):
         return p.shape
 
     def _passthrough(self, p: QuantParameter) -> bool:
         return False
+
+
+@_serialized
+def _apply_fused(channel: "_CodecChannel", c_params: QuantParameters, names: List[str], where: str, models,
+                 inplace: bool, alpha: float, beta: float):
+    """One fused decode + axpby / scale over the entries `names` (receive_axpby, receive_scaled,
+    receive_scaled_add_): the payload staged once into an aligned bucket (``_apply_payload``), then
+      where == "cuda": one launch over pointer tables straight to the K models' tensors, writing the models
+                       themselves (inplace) or new device tensors;
+      where == "cpu":  ADFL's own pattern (get_model_parameters hands out CPU dicts): per model, its tensors
+                       staged into a bucket of the same layout, one launch over the two flat buckets, and the
+                       result copied back into the model (inplace) or handed out as owned CPU tensors.
+    models None: SCALE (no base). Returns the new tensors of the one model (not inplace), else None."""
+    st = _staging()
+    dev = st.device
+    stream = torch.cuda.current_stream(dev)
+    lay, launch = channel._apply_payload(c_params, names, st)
+    shapes = [torch.Size(channel._apply_shape(c_params.params[n])) for n in names]
+    outs = None
+    with torch.no_grad():
+        if where == "cuda":
+            bases = None if models is None else [[m[n] for n in names] for m in models]
+            if inplace:
+                launch(bases, bases, alpha, beta)
+            else:
+                outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+                launch(bases, [outs], alpha, beta)
+            # the next call's host gather rewrites the pinned staging this call's H2D reads from
+            stream.synchronize()
+            return outs
+        out_dev = st.buf("ax_out", lay.total, torch.float32)
+        if models is None:
+            launch(None, out_dev, alpha, beta)
+            return _hand_out(out_dev, lay, shapes, [True] * len(names), st, "ax_out")
+        for m in models:
+            tensors = [m[n] for n in names]
+            base_dev = _stage_in(tensors, lay, st, "ax_base", torch.float32)
+            launch(base_dev, out_dev, alpha, beta)
+            if inplace:
+                _stage_out(out_dev, lay, st, "ax_out", tensors)
+            else:
+                outs = _hand_out(out_dev, lay, shapes, [True] * len(names), st, "ax_out")
+    return outs
 
 
 class _Unidirectional:

@@ -19,6 +19,7 @@ I32 = ctypes.c_int32
 I64 = ctypes.c_int64
 U64 = ctypes.c_uint64
 INT = ctypes.c_int
+F32 = ctypes.c_float
 
 ALIGN_ELEMS = 64     # ADFL_SLQ_ALIGN_ELEMS
 CHUNK_ELEMS = 8192   # ADFL_SLQ_CHUNK_ELEMS
@@ -68,6 +69,9 @@ SIGNATURES = {
     "adfl_slq_dequantize_mean_self": (INT, [P, I64, I32, I64, P, I64, I32, P, P, P]),
     "adfl_slq_dequantize_mean_self_int4": (INT, [P, I64, I32, I64, P, I64, I32, P, P, P]),
     "adfl_slq_dequantize_add_batched": (INT, [P, P, I64, P, P, I32, I32, P]),
+    "adfl_slq_dequantize_axpby_batched": (INT, [P, P, I64, P, P, P, I32, I32, F32, F32, P]),
+    "adfl_slq_dequantize_axpby_batched_int4": (INT, [P, P, I64, P, P, P, I32, I32, F32, F32, P]),
+    "adfl_stoch_dequantize_axpby_batched": (INT, [I32, P, P, P, I64, INT, P, P, P, P, I32, I32, F32, F32, P]),
     "adfl_slq_dequantize_mean_batched": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
     "adfl_slq_dequantize_mean_batched_int4": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
     "adfl_slq_encode_delta_batched": (INT, [P, P, P, I64, INT, P, P, P, P]),

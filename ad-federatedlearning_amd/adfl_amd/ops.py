@@ -10,6 +10,8 @@ synchronises. Semantics are the reference's, bit for bit:
 * ``encode_int4`` / ``decode_int4`` / ``pack_int4`` / ``unpack_int4`` — Src/ADFL/compression.py:35-66
 * ``encode_delta_batched`` / ``encode_delta_batched_int4`` — ``diff_parameters(prev, new)`` (Src/ADFL/model.py:350-358)
   followed by the same per-tensor encode, the difference formed in registers and never written
+* ``dequantize_axpby_batched`` — the asynchronous server's update step: decode fused with ``add_parameters(g, decoded,
+  alpha, beta)`` (Src/ADFL/model.py:326-334; FedAsync, Simple DELTA) or FedBuff's scaling (Strategy/fed_buff.py:72-80)
 * ``dequantize_mean`` — the peer mean after the exchange (Examples/ray_ad.py:188); ``dequantize_mean_batched``
   the same over bucketed payloads with per-tensor scales
 
@@ -17,7 +19,7 @@ The same ops are registered as PyTorch custom ops ``torch.ops.adfl.*`` (with fak
 they trace under torch.compile) at the bottom of this file: slq_absmax, slq_encode / slq_decode,
 slq_encode_int4 / slq_decode_int4, slq_encode_batched / slq_decode_batched and their _int4 variants over
 caller-placed tensors (host offsets / sizes), slq_encode_delta_batched (+ _int4) over two such flat buffers, pack_int4 / unpack_int4, slq_dequantize_mean and
-slq_dequantize_mean_batched (+ _int4).
+slq_dequantize_mean_batched (+ _int4); and, as ``torch.ops.adfl_apply.*``, slq_decode_axpby_batched (+ _int4).
 """
 
 import os
@@ -476,6 +478,76 @@ def dequantize_add_batched(q: torch.Tensor, scales: torch.Tensor, layout: Bucket
     # `table` may be freed on return: the caching allocator only reuses it for later work on this stream
 
 
+def _apply_side(side, layout: BucketLayout, dev: torch.device, what: str):
+    """One side (bases or outputs) of a fused decode + axpby as (int64 pointers, ntargets). `side` is one flat
+    fp32 device bucket in `layout` (one target: pointer t = bucket + offset t; 16-byte aligned base), or K
+    sequences of T contiguous, 16-byte aligned fp32 device tensors of the layout's sizes."""
+    if isinstance(side, torch.Tensor):
+        if (not side.is_cuda or side.device != dev or side.dtype != torch.float32 or not side.is_contiguous()
+                or side.numel() < layout.total or side.data_ptr() % 16):
+            raise ValueError(f"dequantize_axpby_batched: {what} bucket must be a contiguous, 16-byte aligned fp32 "
+                             f"tensor of >= {layout.total} elements on {dev}")
+        return side.data_ptr() + 4 * layout.offsets, 1
+    models = list(side)
+    if not models:
+        raise ValueError(f"dequantize_axpby_batched: {what} is empty")
+    ptrs = []
+    for k, model in enumerate(models):
+        if len(model) != layout.ntensors:
+            raise ValueError(f"dequantize_axpby_batched: {what} {k} has {len(model)} tensors, layout "
+                             f"{layout.ntensors}")
+        for t, (x, n) in enumerate(zip(model, layout.sizes.tolist())):
+            if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.device != dev or x.dtype != torch.float32
+                    or not x.is_contiguous() or x.numel() != n or x.data_ptr() % 16):
+                raise ValueError(f"dequantize_axpby_batched: {what} {k}/{t} must be a contiguous, 16-byte aligned "
+                                 f"fp32 tensor of {n} elements on {dev}")
+            ptrs.append(x.data_ptr())
+    return np.asarray(ptrs, dtype=np.int64), len(models)
+
+
+def apply_tables(bases, outs, layout: BucketLayout, dev: torch.device):
+    """(device table of base pointers or None, device table of output pointers, ntargets) for the fused decode
+    + axpby entries, after checking both sides against the layout (ValueError before anything is launched).
+    An output may be its own base (in place); any other overlap between a base and an output is undefined."""
+    o_ptrs, k = _apply_side(outs, layout, dev, "outs")
+    if bases is None:
+        return None, torch.from_numpy(np.ascontiguousarray(o_ptrs)).to(dev, non_blocking=True), k
+    b_ptrs, kb = _apply_side(bases, layout, dev, "bases")
+    if kb != k:
+        raise ValueError(f"dequantize_axpby_batched: {kb} bases for {k} outputs")
+    both = torch.from_numpy(np.ascontiguousarray(np.concatenate([b_ptrs, o_ptrs]))).to(dev, non_blocking=True)
+    return both[:b_ptrs.size], both[b_ptrs.size:], k
+
+
+def dequantize_axpby_batched(q: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, bases, outs,
+                             alpha: float, beta: float, packed: bool = False) -> None:
+    """Fused decode + axpby, the asynchronous server's update step (adfl_slq_dequantize_axpby_batched): for every
+    target k and tensor t, with d = fp32(scales[t] * q_t),
+        outs[k][t] = fp32(fp32(alpha * bases[k][t]) + fp32(beta * d))     bases given
+        outs[k][t] = fp32(beta * d)                                       bases is None (FedBuff's mul_)
+    three separately rounded fp32 operations — add_parameters(g, decoded, 1 - a_t, a_t) of FedAsync
+    (Src/ADFL/Strategy/fed_async.py:80-81), add_parameters(g, decoded, 1, 1) of Simple DELTA (simple.py:100) and
+    FedBuff's scale then add_parameters_inpace(buffer, decoded, 1, 1) (fed_buff.py:72-80), bit for bit.
+
+    bases / outs: each one flat fp32 device bucket in `layout`, or K sequences of T contiguous, 16-byte aligned
+    fp32 device tensors with layout.sizes[t] elements; outs[k][t] may be bases[k][t] itself (in place).
+    packed=True: q is an int4-packed bucket payload (even tensor offsets)."""
+    q = _dev(q, "q")
+    dev = q.device
+    if packed:
+        _require_even_offsets(layout)
+    if q.numel() * q.element_size() < ((layout.total + 1) // 2 if packed else layout.total):
+        raise ValueError("dequantize_axpby_batched: payload smaller than the layout")
+    scales = _f32_on(scales, layout.ntensors, dev, "scales")
+    b_tab, o_tab, k = apply_tables(bases, outs, layout, dev)
+    lib = _lib.load()
+    fn = lib.adfl_slq_dequantize_axpby_batched_int4 if packed else lib.adfl_slq_dequantize_axpby_batched
+    check(fn(q.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks, scales.data_ptr(),
+             b_tab.data_ptr() if b_tab is not None else None, o_tab.data_ptr(), layout.ntensors, k,
+             float(alpha), float(beta), _stream(dev)))
+    # the tables may be freed on return: the caching allocator only reuses them for later work on this stream
+
+
 def dequantize_mean_batched(q_rows: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, *,
                             out: Optional[torch.Tensor] = None, self_row: int = -1,
                             self_x: Optional[torch.Tensor] = None, packed: bool = False) -> torch.Tensor:
@@ -915,3 +987,44 @@ def slq_dequantize_mean_batched_int4_op(packed_rows: torch.Tensor, scales: torch
 @slq_dequantize_mean_batched_int4_op.register_fake
 def _(packed_rows, scales, offsets, sizes, n, self_row=-1, self_x=None):
     return packed_rows.new_empty((n,), dtype=torch.float32)
+
+
+def _decode_axpby_flat(q: torch.Tensor, scales: torch.Tensor, base: torch.Tensor, lay: BucketLayout, alpha: float,
+                       beta: float, packed: bool) -> torch.Tensor:
+    """slq_decode_axpby_batched's body: a new fp32 bucket shaped like `base`."""
+    base = base.reshape(-1)
+    if base.dtype != torch.float32:
+        raise ValueError(f"slq_decode_axpby_batched: the base bucket must be float32, got {base.dtype}")
+    if base.numel() < lay.total:
+        raise ValueError("slq_decode_axpby_batched: base bucket smaller than the layout")
+    out = _filled(base.numel(), torch.float32, base.device, lay)
+    dequantize_axpby_batched(q.reshape(-1), scales, lay, _dev(base, "base"), out, alpha, beta, packed=packed)
+    return out
+
+
+# The fused decode + axpby ops live in their own namespace, torch.ops.adfl_apply.*: the set of torch.ops.adfl.*
+# ops is pinned (tests/test_stoch_delta_abi.py counts them), and that set is the codec proper.
+@torch.library.custom_op("adfl_apply::slq_decode_axpby_batched", mutates_args=())
+def slq_decode_axpby_batched_op(q: torch.Tensor, scales: torch.Tensor, base: torch.Tensor, offsets: torch.Tensor,
+                                sizes: torch.Tensor, alpha: float, beta: float) -> torch.Tensor:
+    """fp32(fp32(alpha * base) + fp32(beta * decode(q))) per tensor of a caller-placed layout, as a new bucket
+    shaped like `base` (FedAsync / Simple DELTA / FedBuff's server step; positions no tensor owns are zero)."""
+    return _decode_axpby_flat(q, scales, base, layout_for(offsets, sizes), alpha, beta, False)
+
+
+@slq_decode_axpby_batched_op.register_fake
+def _(q, scales, base, offsets, sizes, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_decode_axpby_batched_int4", mutates_args=())
+def slq_decode_axpby_batched_int4_op(packed: torch.Tensor, scales: torch.Tensor, base: torch.Tensor,
+                                     offsets: torch.Tensor, sizes: torch.Tensor, alpha: float,
+                                     beta: float) -> torch.Tensor:
+    """slq_decode_axpby_batched over an int4-packed bucket payload (even tensor offsets)."""
+    return _decode_axpby_flat(packed, scales, base, layout_for(offsets, sizes), alpha, beta, True)
+
+
+@slq_decode_axpby_batched_int4_op.register_fake
+def _(packed, scales, base, offsets, sizes, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)

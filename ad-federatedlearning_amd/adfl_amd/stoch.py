@@ -594,3 +594,59 @@ def stoch_decode_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: to
 @stoch_decode_batched_op.register_fake
 def _(levels, signs, norms, mins, offsets, sizes, codec, bits):
     return levels.new_empty((levels.numel(),), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# fused decode + axpby: the asynchronous server's update step (adfl_stoch_dequantize_axpby_batched)
+# ------------------------------------------------------------------------------------------------
+def dequantize_axpby_batched(codec: str, levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                             layout: BucketLayout, bits: int, bases, outs, alpha: float, beta: float, *,
+                             mins: Optional[torch.Tensor] = None) -> None:
+    """ops.dequantize_axpby_batched for the stochastic codecs: with d the codec's decode of one bucket payload
+    (+0 for a tensor whose norm is 0), outs[k][t] = fp32(fp32(alpha * bases[k][t]) + fp32(beta * d)), or
+    fp32(beta * d) when bases is None — FedAsync (Src/ADFL/Strategy/fed_async.py:80-81), Simple DELTA
+    (simple.py:100) and FedBuff (fed_buff.py:72-80) over quant.py:243-252 / :385-398 / :537-545. bases / outs as
+    ops.dequantize_axpby_batched takes them; levels / signs byte planes of >= layout.total, norms (RQSGD: mins)
+    one fp32 per tensor."""
+    from .ops import _f32_on, apply_tables
+    _check_codec(codec)
+    levels, signs = _dev(levels, "levels"), _dev(signs, "signs")
+    dev = levels.device
+    if (levels.element_size() != 1 or signs.element_size() != 1 or levels.numel() < layout.total
+            or signs.numel() < layout.total or signs.device != dev):
+        raise ValueError(f"adfl_amd.stoch: levels / signs must be byte planes of >= {layout.total} on one device")
+    norms = _f32_on(norms, layout.ntensors, dev, "norms")
+    if codec == "rqsgd":
+        if mins is None:
+            raise ValueError("adfl_amd.stoch: RQSGD needs mins")
+        mins = _f32_on(mins, layout.ntensors, dev, "mins")
+    else:
+        mins = None
+    b_tab, o_tab, k = apply_tables(bases, outs, layout, dev)
+    check(_lib.load().adfl_stoch_dequantize_axpby_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signs.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        bits, norms.data_ptr(), mins.data_ptr() if mins is not None else None,
+        b_tab.data_ptr() if b_tab is not None else None, o_tab.data_ptr(), layout.ntensors, k, float(alpha),
+        float(beta), _stream(dev)))
+
+
+@torch.library.custom_op("adfl_apply::stoch_decode_axpby_batched", mutates_args=())
+def stoch_decode_axpby_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor, mins: torch.Tensor,
+                                  base: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str,
+                                  bits: int, alpha: float, beta: float) -> torch.Tensor:
+    """fp32(fp32(alpha * base) + fp32(beta * decode)) per tensor of stoch_encode_batched's planes, as a new
+    bucket shaped like `base` (mins used by RQSGD only; positions no tensor owns are zero)."""
+    from .ops import _filled, layout_for
+    _check_codec(codec)
+    lay = layout_for(offsets, sizes)
+    levels, signs, base = levels.reshape(-1), signs.reshape(-1), base.reshape(-1)
+    if base.dtype != torch.float32 or base.numel() < lay.total:
+        raise ValueError("stoch_decode_axpby_batched: base must be an fp32 bucket of at least the layout's extent")
+    out = _filled(base.numel(), torch.float32, base.device, lay)
+    dequantize_axpby_batched(codec, levels, signs, norms, lay, bits, _dev(base, "base"), out, alpha, beta, mins=mins)
+    return out
+
+
+@stoch_decode_axpby_batched_op.register_fake
+def _(levels, signs, norms, mins, base, offsets, sizes, codec, bits, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)

@@ -35,6 +35,7 @@
 #include <cstring>
 
 #include "adfl_slq.h"
+#include "apply_device.h"  // the axpby / scale tail shared with stoch_codec.hip
 #include "slq_device.h"  // the device helpers shared with slq_delta.hip
 #include "torch_sum_order.h"
 
@@ -746,6 +747,49 @@ __global__ __launch_bounds__(kBlock) void k_dequantize_add_batched(const int8_t*
   }
 }
 
+// Decode + axpby / scale — the asynchronous server's update step on every client update: FedAsync's
+// add_parameters(g, decoded, 1 - a_t, a_t) (Strategy/fed_async.py:80-81), Simple DELTA's add_parameters(g,
+// decoded, 1, 1) (Strategy/simple.py:100) and FedBuff's tensor.float().mul_(f) then add_parameters_inpace(buffer,
+// decoded, 1, 1) (Strategy/fed_buff.py:72-80). k_dequantize_add_batched's shape: when the tensor's offset in the
+// bucket is a multiple of 4 (block-uniform: every chunk of a tensor shares its offset's residue mod 4) the chunk's
+// payload is loaded whole (a thread's group k is payload dword k; int4: halfword k), decoded once into 8 float4
+// per thread, and apply_chunk (apply_device.h) reads each target's base slice, combines and writes that target's
+// output with 16-byte accesses. Any other offset, and a target that is not 16-byte aligned, goes element by
+// element with the same results. PACKED: an int4 bucket (pack_4bit layout, even tensor offsets).
+template <bool PACKED>
+__global__ __launch_bounds__(kBlock) void k_dequantize_axpby_batched(const uint8_t* __restrict__ q,
+                                                                     const adfl_slq_chunk* __restrict__ chunks,
+                                                                     const float* __restrict__ scales,
+                                                                     ApplyTargets a) {
+  static_assert(kApplyBlock == kBlock, "apply_chunk's thread layout");
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const float s = scales[c.tensor];
+  const int64_t in_tensor = (int64_t)(blockIdx.x - c.first_chunk) * ADFL_SLQ_CHUNK_ELEMS;
+  const bool grouped = (c.start & 3) == 0;
+  auto dec1 = [&](int i) -> float {
+    const int64_t e = c.start + i;
+    if (!PACKED) return s * (float)(int8_t)q[e];
+    float e0, e1;
+    dequant_byte_int4(q[e >> 1], s, e0, e1);
+    return (e & 1) ? e1 : e0;
+  };
+  float4 dv[kApplyGroups];
+  if (grouped) {
+    const int n4 = c.len >> 2;
+    const uint8_t* qc = PACKED ? q + (c.start >> 1) : q + c.start;  // 4-byte (int4: 2-byte) aligned
+    uint32_t w[kApplyGroups];
+#pragma unroll
+    for (int j = 0; j < kApplyGroups; ++j) {  // every load of the chunk before the first use
+      const int k = (int)threadIdx.x + j * kBlock;
+      w[j] = k >= n4 ? 0u : PACKED ? (uint32_t) reinterpret_cast<const uint16_t*>(qc)[k]
+                                   : reinterpret_cast<const uint32_t*>(qc)[k];
+    }
+#pragma unroll
+    for (int j = 0; j < kApplyGroups; ++j) dv[j] = PACKED ? dequant2_int4(w[j], s) : dequant4(w[j], s);
+  }
+  apply_chunk(dv, grouped, c, in_tensor, a, dec1);
+}
+
 // Quantization-error statistics of a bucket against its own payload (worker.py:186-189 computes
 // parameter_relative_mse and parameter_cosine_similarity from a full decode; here they are four sums
 // per chunk, fp64): S0 = sum (x - s*q)^2, S1 = sum x^2, S2 = sum x*(s*q), S3 = sum (s*q)^2.
@@ -1195,6 +1239,29 @@ int adfl_slq_dequantize_add_batched(const int8_t* d_q, const adfl_slq_chunk* d_c
   if (!aligned16(d_q)) return ADFL_E_ALIGN;
   hipLaunchKernelGGL(k_dequantize_add_batched, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_q,
                      d_chunks, d_scales, d_targets, (int)ntensors, (int)ntargets);
+  return launch_status();
+}
+
+int adfl_slq_dequantize_axpby_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                      const float* d_scales, const float* const* d_base, float* const* d_out,
+                                      int32_t ntensors, int32_t ntargets, float alpha, float beta, void* stream) {
+  if (!d_q || !d_scales || apply_bad_args(d_chunks, nchunks, d_out, ntensors, ntargets)) return ADFL_E_ARG;
+  if (!aligned16(d_q)) return ADFL_E_ALIGN;
+  const ApplyTargets a{d_base, d_out, (int)ntensors, (int)ntargets, alpha, beta};
+  hipLaunchKernelGGL(k_dequantize_axpby_batched<false>, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint8_t*>(d_q), d_chunks, d_scales, a);
+  return launch_status();
+}
+
+int adfl_slq_dequantize_axpby_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                           const float* d_scales, const float* const* d_base, float* const* d_out,
+                                           int32_t ntensors, int32_t ntargets, float alpha, float beta,
+                                           void* stream) {
+  if (!d_packed || !d_scales || apply_bad_args(d_chunks, nchunks, d_out, ntensors, ntargets)) return ADFL_E_ARG;
+  if (!aligned16(d_packed)) return ADFL_E_ALIGN;
+  const ApplyTargets a{d_base, d_out, (int)ntensors, (int)ntargets, alpha, beta};
+  hipLaunchKernelGGL(k_dequantize_axpby_batched<true>, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream,
+                     d_packed, d_chunks, d_scales, a);
   return launch_status();
 }
 

@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "adfl_stoch.h"
+#include "apply_device.h"  // the axpby / scale tail shared with slq_codec.hip
 #include "cnat_log2_table.h"
 #include "philox.h"
 #include "stoch_device.h"
@@ -835,6 +836,54 @@ __global__ __launch_bounds__(kBlock) void k_stoch_dequantize(const uint8_t* __re
   if (i >= 0) oc[i] = decode_exact<KIND>(lv[i], sg[i], norm, mn, s);
 }
 
+// Decode + axpby / scale for the three stochastic codecs — the asynchronous server's update step
+// (Strategy/fed_async.py:80-81, simple.py:100, fed_buff.py:72-80; slq_codec.hip k_dequantize_axpby_batched is the
+// SLQ form). When the tensor's offset in the bucket is a multiple of 4 (block-uniform) the chunk's level and sign
+// dwords are loaded whole and decoded once (decode4, the decode kernel's values; +0 for a tensor whose norm is 0)
+// into 8 float4 per thread, and apply_chunk reads each target's base slice, combines and writes that target's
+// output with 16-byte accesses. Any other offset, and a target that is not 16-byte aligned, goes element by
+// element (decode_exact) with the same results.
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void k_stoch_dequantize_axpby(const uint8_t* __restrict__ levels,
+                                                                   const uint8_t* __restrict__ signs,
+                                                                   const adfl_slq_chunk* __restrict__ chunks,
+                                                                   const float* __restrict__ norms,
+                                                                   const float* __restrict__ mins, float s,
+                                                                   ApplyTargets a) {
+  static_assert(kApplyBlock == kBlock && kApplyGroups == kPer, "apply_chunk's thread layout");
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const float norm = norms[c.tensor];
+  const float mn = KIND == 1 ? mins[c.tensor] : 0.0f;
+  const int64_t in_tensor = (int64_t)(blockIdx.x - c.first_chunk) * ADFL_SLQ_CHUNK_ELEMS;
+  const bool grouped = (c.start & 3) == 0;
+  const uint8_t* lv = levels + c.start;
+  const uint8_t* sg = signs + c.start;
+  auto dec1 = [&](int i) -> float {  // quant.py:248-249 / :390-391 / :542-543: zeros when the norm is 0
+    return norm == 0.0f ? 0.0f : decode_exact<KIND>(lv[i], sg[i], norm, mn, s);
+  };
+  float4 dv[kPer];
+  if (grouped) {
+    const int n4 = c.len >> 2;
+    uint32_t L[kPer], G[kPer];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {  // every load of the chunk before the first use
+      const int k = (int)threadIdx.x + j * kBlock;
+      L[j] = k < n4 ? reinterpret_cast<const uint32_t*>(lv)[k] : 0u;
+      G[j] = k < n4 ? reinterpret_cast<const uint32_t*>(sg)[k] : 0u;
+    }
+    if (norm == 0.0f) {  // block-uniform
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) dv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      const Div dd = make_div(s);
+#pragma unroll
+      for (int j = 0; j < kPer; ++j)  // every lane calls (a wave ballot inside)
+        dv[j] = decode4<KIND>(L[j], G[j], norm, mn, dd, s, (int)threadIdx.x + j * kBlock < n4);
+    }
+  }
+  apply_chunk(dv, grouped, c, in_tensor, a, dec1);
+}
+
 // Server-side mean of K clients' payloads: simple_aggregate (Src/ADFL/model.py:221-234) over the K decodes
 // (quant.py:243-252 / :385-398 / :537-545), the synchronous server's aggregate of K updates:
 //   out[i] = fp32(torch-order sum over r of d_r[i]) / K   (the division correctly rounded)
@@ -1171,6 +1220,27 @@ int adfl_stoch_dequantize_mean_batched(int32_t codec, const uint8_t* d_levels, c
                                               : (deep ? k_stoch_dequantize_mean<2, true> : k_stoch_dequantize_mean<2, false>);
   hipLaunchKernelGGL(kern, grid, block, 0, st, d_levels, sg, row_stride_bytes, k, d_chunks, d_norms, d_mins, norm_stride,
                      s, d_out);
+  return launch_status();
+}
+
+int adfl_stoch_dequantize_axpby_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                        const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                        const float* d_norms, const float* d_mins, const float* const* d_base,
+                                        float* const* d_out, int32_t ntensors, int32_t ntargets, float alpha,
+                                        float beta, void* stream) {
+  if (codec != ADFL_CODEC_QSGD && codec != ADFL_CODEC_RQSGD && codec != ADFL_CODEC_CNAT) return ADFL_E_ARG;
+  if (!d_levels || !d_signs || !d_norms || (codec == ADFL_CODEC_RQSGD && !d_mins) ||
+      apply_bad_args(d_chunks, nchunks, d_out, ntensors, ntargets))
+    return ADFL_E_ARG;
+  if (codec != ADFL_CODEC_CNAT && check_bits(bits)) return ADFL_E_ARG;  // bits unused for CNAT, as the mean
+  if (!aligned16(d_levels) || !aligned16(d_signs)) return ADFL_E_ALIGN;
+  const float s = codec == ADFL_CODEC_CNAT ? 1.0f : levels_f(bits);
+  const ApplyTargets a{d_base, d_out, (int)ntensors, (int)ntargets, alpha, beta};
+  auto kern = codec == ADFL_CODEC_QSGD    ? k_stoch_dequantize_axpby<0>
+              : codec == ADFL_CODEC_RQSGD ? k_stoch_dequantize_axpby<1>
+                                          : k_stoch_dequantize_axpby<2>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_levels,
+                     reinterpret_cast<const uint8_t*>(d_signs), d_chunks, d_norms, d_mins, s, a);
   return launch_status();
 }
 

@@ -233,6 +233,34 @@ int adfl_slq_dequantize_add_batched(const int8_t* d_q, const adfl_slq_chunk* d_c
                                     const float* d_scales, float* const* d_targets, int32_t ntensors,
                                     int32_t ntargets, void* stream);
 
+/* Fused decode + axpby: the asynchronous server's update step on every client update. For every target k and
+ * tensor t, with d = fp32(scale_t * q[i]) (the decode's value) and y = base_k[t][i],
+ *   AXPBY (d_base != NULL)  out_k[t][i] = fp32(fp32(alpha * y) + fp32(beta * d))
+ *   SCALE (d_base == NULL)  out_k[t][i] = fp32(beta * d)          (alpha unused; -0.0 keeps its sign)
+ * three separately rounded fp32 operations, never an FMA — what torch's CPU kernels compute for
+ *   add_parameters(g, decoded, 1 - a_t, a_t)        FedAsync          (Src/ADFL/Strategy/fed_async.py:80-81)
+ *   add_parameters(g, decoded, 1.0, 1.0)            Simple, DELTA     (Src/ADFL/Strategy/simple.py:100)
+ *   tensor.float().mul_(f); add_parameters_inpace(buffer, decoded, 1, 1, False)
+ *                                                   FedBuff           (Src/ADFL/Strategy/fed_buff.py:72-80)
+ * (Src/ADFL/model.py:326-347) over on_server_receive's decode (Src/ADFL/Server/common.py:228-236). There is no
+ * shortcut for alpha or beta == 0 (0 * inf is NaN in torch too); denormal products are kept. The payload is
+ * read once for all targets; each base is read once and each output written once.
+ *   d_q, d_chunks  a bucketed payload, any tensor offsets, as adfl_slq_dequantize_add_batched
+ *   d_base, d_out  DEVICE arrays of ntargets * ntensors device pointers, laid out as d_targets above. Two flat
+ *                  buckets are bucket + offset[t]. d_out[i] == d_base[i] updates in place; any other overlap
+ *                  is undefined. Pointers that are not 16-byte aligned take element-wise accesses.
+ * ADFL_E_ARG and nothing launched for a null d_q / d_chunks / d_scales / d_out, nchunks outside
+ * [1, INT32_MAX], ntensors < 1 or ntargets < 1. */
+int adfl_slq_dequantize_axpby_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                      const float* d_scales, const float* const* d_base, float* const* d_out,
+                                      int32_t ntensors, int32_t ntargets, float alpha, float beta, void* stream);
+/* Same over an int4-packed bucket payload (adfl_slq_encode_batched_int4's: every tensor offset EVEN, flat
+ * element e in byte e/2, high nibble for even e; Src/ADFL/compression.py:52-66 then the same dequantize). */
+int adfl_slq_dequantize_axpby_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                           const float* d_scales, const float* const* d_base, float* const* d_out,
+                                           int32_t ntensors, int32_t ntargets, float alpha, float beta,
+                                           void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Delta encode — the send side of a CommType.DELTA round: diff_parameters(prev, new)
  * (Src/ADFL/model.py:350-358: new - prev per tensor) followed by SLQChannel._quantize_params

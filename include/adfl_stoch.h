@@ -148,6 +148,23 @@ int adfl_stoch_dequantize_mean_batched(int32_t codec, const uint8_t* d_levels, c
                                        int64_t nchunks, int bits, const float* d_norms, const float* d_mins,
                                        int64_t norm_stride, float* d_out, void* stream);
 
+/* Fused decode + axpby for the three stochastic codecs: adfl_slq_dequantize_axpby_batched (adfl_slq.h) with d the
+ * codec's decode (quant.py:243-252 / :385-398 / :537-545; +0 for a tensor whose norm is 0) — FedAsync's
+ * add_parameters(g, decoded, 1 - a_t, a_t) (Src/ADFL/Strategy/fed_async.py:80-81), Simple DELTA's (1, 1)
+ * (Strategy/simple.py:100) and FedBuff's mul_(f) then add_parameters_inpace(buffer, decoded, 1, 1)
+ * (Strategy/fed_buff.py:72-80):
+ *   d_base != NULL  out_k[t][i] = fp32(fp32(alpha * base_k[t][i]) + fp32(beta * d))
+ *   d_base == NULL  out_k[t][i] = fp32(beta * d)
+ * codec: ADFL_CODEC_* (bits unused for CNAT; d_mins for RQSGD only). d_levels / d_signs 16-byte aligned; d_base /
+ * d_out device arrays of ntargets * ntensors pointers, d_out[i] == d_base[i] in place. ADFL_E_ARG and nothing
+ * launched for an unknown codec, a null pointer, nchunks outside [1, INT32_MAX], bits outside [1, 16],
+ * ntensors < 1 or ntargets < 1. */
+int adfl_stoch_dequantize_axpby_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                        const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                        const float* d_norms, const float* d_mins, const float* const* d_base,
+                                        float* const* d_out, int32_t ntensors, int32_t ntargets, float alpha,
+                                        float beta, void* stream);
+
 /* One-launch encodes (same outputs, bit for bit) for a bucket whose tensors ALL have at most
  * ADFL_SLQ_RESIDENT_CHUNKS chunks: d_work / nwork is the work list of adfl_slq_build_encode_work (the first
  * chunk of every tensor; nwork == 0 when some tensor is larger). A 1024-thread block holds one whole tensor

@@ -21,6 +21,11 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             the same for a log-uniform layout (the two-pass form) and, wall time only, for CPU dicts
   delta_stoch  the same protocol for QSGDChannel / RQSGDChannel / CNATChannel(8).send_delta, and in HIP events the
             two-source RQSGD encode and bucket_diff against torch._foreach_sub + gather (+ rqsgd_encode_batched)
+  apply     the asynchronous server's update step (FedAsync's coefficients at staleness 1), SLQChannel(8), on the C3
+            dict and on one 2^28-element tensor: the fused decode + axpby over a device-resident base against the
+            decode launch followed by torch's alpha * g + beta * d on the device (HIP events, Infinity Cache
+            flushed); and host to host, receive_axpby against on_server_receive + the reference's CPU
+            add_parameters (wall). A parity flag per leg; no threshold
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -1009,6 +1014,119 @@ def mode_delta_stoch(args, world, rank, dev):
             "steps": args.steps, "c3_equal": eq, "c3_loguniform": log}
 
 
+def _bits_equal(a, b) -> bool:
+    a, b = a.detach().cpu().reshape(-1), b.detach().cpu().reshape(-1)
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+def _apply_leg(sizes, args, dev, junk, host_steps):
+    """One layout of the apply leg, SLQChannel(8), FedAsync's coefficients at staleness 1.
+    device: ops.dequantize_axpby_batched over a device-resident base (new outputs) against the route without it —
+            the decode launch, then torch's (alpha * g) + (beta * d) on the device, over the flat bucket (torch's
+            best case: three launches, not three per tensor). HIP events, Infinity Cache flushed before each.
+    host:   receive_axpby on a CPU base against on_server_receive + the reference's CPU add_parameters, wall."""
+    from adfl_amd import ops
+    from adfl_amd.Channel import SLQChannel
+    alpha_t = 0.6 * 2 ** -0.5
+    alpha, beta = 1 - alpha_t, alpha_t
+    lay = ops.BucketLayout(list(sizes))
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(lay.total, device=dev, generator=g) * 1e-2
+    base = torch.randn(lay.total, device=dev, generator=g)
+    q, s = ops.encode_batched(x, lay, 8)
+    del x
+    out = torch.empty(lay.total, device=dev)
+    dec = torch.empty(lay.total, device=dev)
+
+    def k_fused(ev):
+        junk.amax()
+        if ev is not None:
+            ev[0].record()
+        ops.dequantize_axpby_batched(q, s, lay, base, out, alpha, beta)
+        if ev is not None:
+            ev[1].record()
+
+    res2 = []
+
+    def k_two_step(ev):
+        junk.amax()
+        if ev is not None:
+            ev[0].record()
+        d = ops.decode_batched(q, s, lay, out=dec)
+        r = (alpha * base) + (beta * d)
+        if ev is not None:
+            ev[1].record()
+        res2[:] = [r]
+
+    k_fused(None), k_two_step(None)
+    torch.cuda.synchronize()
+    own = torch.zeros(lay.total, dtype=torch.bool)
+    for o, n in zip(lay.offsets.tolist(), lay.sizes.tolist()):
+        own[o:o + n] = True
+    own = own.to(dev)
+    parity = _bits_equal(out[own], res2[0][own])
+    _, evs = timed(k_fused, args.steps, args.warmup, 1, 2)
+    kf = _median([e[0].elapsed_time(e[1]) for e in evs])
+    _, evs = timed(k_two_step, args.steps, args.warmup, 1, 2)
+    ku = _median([e[0].elapsed_time(e[1]) for e in evs])
+    n = int(sum(sizes))
+    res = {"tensors": len(sizes), "elements": n, "device_parity": parity, "fused_ms": round(kf, 4),
+           "decode_then_torch_ms": round(ku, 4), "device_ratio": round(ku / kf, 3),
+           # bytes the fused kernel must move: payload 1, base 4, result 4
+           "fused_frac_moved": round(9 * n / (kf * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    del out, dec, res2[:]
+
+    # host to host: ADFL's own pattern (a CPU g_params, a CPU payload, a CPU result)
+    ch = SLQChannel(8)
+    shapes = [(1, m) for m in sizes]
+    upd = {f"layer{i:03d}.weight": (torch.randn(sh) * 1e-2) for i, sh in enumerate(shapes)}
+    g_cpu = {k: torch.randn(v.shape) for k, v in upd.items()}
+    for i in range(len(sizes) if len(sizes) > 1 else 0):
+        upd[f"layer{i:03d}.bias"], g_cpu[f"layer{i:03d}.bias"] = torch.randn(64) * 1e-2, torch.randn(64)
+    c, _ = ch.on_client_send(upd)
+    del upd
+
+    def fused():
+        return ch.receive_axpby(c, g_cpu, alpha, beta)[0]
+
+    def two_step():
+        d, _ = ch.on_server_receive(c)
+        with torch.no_grad():   # add_parameters (model.py:326-334) on the same box
+            return {k: (alpha * g_cpu[k]) + (beta * d[k]) for k in d}
+
+    def wall(fn, steps):
+        ts = []
+        for _ in range(steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return _median(ts)
+
+    a, b = fused(), two_step()
+    res["host_parity"] = list(a) == list(b) and all(_bits_equal(a[k], b[k]) for k in a)
+    del a, b
+    res["host_receive_axpby_ms"] = round(wall(fused, host_steps), 3)
+    res["host_receive_then_add_parameters_ms"] = round(wall(two_step, host_steps), 3)
+    res["host_ratio"] = round(res["host_receive_then_add_parameters_ms"] / res["host_receive_axpby_ms"], 3)
+    return res
+
+
+def mode_apply(args, world, rank, dev):
+    """The asynchronous server's update step (FedAsync / Simple DELTA / FedBuff): fused decode + axpby against
+    decode, then torch. No threshold: both times and their ratio are reported with a parity flag per leg."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    c3 = _apply_leg(recipes.bucket_sizes("equal"), args, dev, junk, host_steps=max(3, min(args.steps, 7)))
+    big = _apply_leg([args.elems or 1 << 28], args, dev, junk, host_steps=3)
+    return {"mode": "apply", "metric": "SLQChannel(8) decode + axpby, device-resident base, C3 dict "
+            "(fused kernel, Infinity Cache flushed)", "unit": "ms", "value": c3["fused_ms"],
+            "parity": all(leg[f] for leg in (c3, big) for f in ("device_parity", "host_parity")),
+            "steps": args.steps, "c3_equal": c3, "one_tensor": big}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1016,7 +1134,7 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta", "delta_stoch"], required=True)
+                                      "delta", "delta_stoch", "apply"], required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -1033,7 +1151,7 @@ def main():
     dev = torch.device("cuda", local)
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
-            "delta": mode_delta, "delta_stoch": mode_delta_stoch}[args.mode](
+            "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
