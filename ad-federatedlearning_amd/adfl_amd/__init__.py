@@ -9,6 +9,8 @@ Layout mirrors the reference's ``Src/ADFL`` package for the one hot path this re
                             (``ADFL.compression``'s hot-path functions) on the GPU
 * ``adfl_amd.ops``          device-resident codec ops; ``torch.ops.adfl.*`` custom ops
 * ``adfl_amd.exchange``     one-client-per-GPU peer exchange: encode -> RCCL all-gather -> mean
+* ``adfl_amd.flush``        the buffered servers' flush: ``fedbuff_flush``, ``FadasMoments`` (``ADFL.Strategy``'s
+                            FedBuff / FADAS step on a full buffer); ``torch.ops.adfl_apply.*_flush_batched``
 
 The compute lives in ``libadfl_slq.so`` (``ad-federatedlearning_amd/csrc/slq_codec.hip``, C ABI in
 ``include/adfl_slq.h``). Importing this package loads it and fails loudly if it was not built.
@@ -21,7 +23,9 @@ _lib.load()
 from . import compression, model, ops, stoch  # noqa: E402
 from .Channel import (Channel, CNATChannel, IdentityChannel, PackedSLQChannel, QSGDChannel,  # noqa: E402
                       RQSGDChannel, SLQChannel, UCNATChannel, UQSGDChannel, URQSGDChannel, USLQChannel)
+from . import flush  # noqa: E402  (after Channel: it stages through Channel._staging)
+from .flush import FadasMoments, fedbuff_flush  # noqa: E402
 
 __all__ = ["Channel", "IdentityChannel", "SLQChannel", "USLQChannel", "PackedSLQChannel", "QSGDChannel",
            "UQSGDChannel", "RQSGDChannel", "URQSGDChannel", "CNATChannel", "UCNATChannel", "compression", "model",
-           "ops", "stoch"]
+           "ops", "stoch", "flush", "fedbuff_flush", "FadasMoments"]

@@ -110,6 +110,9 @@ SIGNATURES = {
     "adfl_stoch_quantize_batched_dt": (INT, [I32, I32, P, P, I64, INT, P, P, U64, U64, P, P, P]),
     "adfl_stoch_encode_batched_dt": (INT, [I32, I32, P, P, I64, INT, P, U64, U64, P, I64, P, P, P, P, P]),
     "adfl_philox_uniforms_dt": (INT, [I32, P, I64, I64, U64, U64, P]),
+    # adfl_slq.h: the buffered servers' flush (csrc/server_flush.hip)
+    "adfl_fedbuff_flush_batched": (INT, [P, P, P, P, I64, I32, I32, F32, P]),
+    "adfl_fadas_flush_batched": (INT, [P, P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, F32, F32, F32, F32, P]),
     # adfl_host.h
     "adfl_host_copy": (INT, [P, P, P, I64, I32]),
     "adfl_host_copy_ex": (INT, [P, P, P, I64, I32, I32]),

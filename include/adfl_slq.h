@@ -311,6 +311,54 @@ int adfl_bucket_gather(void* d_bucket, const adfl_slq_chunk* d_chunks, int64_t n
 int adfl_bucket_scatter(const void* d_bucket, const adfl_slq_chunk* d_chunks, int64_t nchunks, void* const* d_dsts,
                         int32_t elem_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The buffered asynchronous servers' flush (csrc/server_flush.hip): what FedBuff and FADAS compute from a full
+ * buffer, one launch for a whole state dict. No payload is involved; the entries sit here because they walk
+ * this header's chunk table. Additions: ADFL_SLQ_ABI_VERSION is unchanged.
+ *
+ * Tables. Every operand is a DEVICE array of ntensors device pointers, one fp32 pointer per tensor, walked
+ * through an adfl_slq_chunk table: chunk c covers elements [in_tensor, in_tensor + len) of tensor c.tensor,
+ * in_tensor = (c - first_chunk) * ADFL_SLQ_CHUNK_ELEMS. Only the table's tensor sizes matter, not its offsets:
+ * separately allocated tensors pass their own pointers, a flat bucket passes bucket + offset[t]. A chunk whose
+ * slice of every table is 16-byte aligned takes 16-byte accesses; any other chunk goes element by element with
+ * identical results. The storages of different operands must not overlap.
+ *
+ * Arithmetic. fp32 throughout, every operation rounded to nearest even on its own (division and square root
+ * correctly rounded, denormals kept), an FMA only where one is written below. Scalars are floats the caller
+ * has rounded once from the Python doubles, as torch rounds a double it applies to an fp32 tensor.
+ * ------------------------------------------------------------------------------------------- */
+
+/* FedBuff's flush (Src/ADFL/Strategy/fed_buff.py:88-92): tensor.float().div_(K), then
+ * add_parameters(g_params, buffer, 1.0, lr). Per element
+ *   b   = buf / (float)K                                  true division, not a reciprocal multiply
+ *   out = fp32(fp32(1.0f * g) + fp32(lr * b))             the three-rounding AXPBY above
+ * Reads d_buf and d_g (both non-temporally), writes d_out. The averaged buffer is NOT written back: the
+ * reference clears the buffer right after the flush (fed_buff.py:96), so nothing reads it.
+ * ADFL_E_ARG and nothing launched for a null table, nchunks outside [1, INT32_MAX], ntensors < 1 or K < 1. */
+int adfl_fedbuff_flush_batched(const float* const* d_buf, const float* const* d_g, float* const* d_out,
+                               const adfl_slq_chunk* d_chunks, int64_t nchunks, int32_t ntensors, int32_t K, float lr,
+                               void* stream);
+
+/* FADAS's flush (Src/ADFL/Strategy/fadas.py:69-73): tensor.float().div_(K), _update_amsgrad and
+ * _compute_model_step. Per element, with m, v, v_hat the moments before the call,
+ *   b      = buf / (float)K
+ *   m'     = fma(b, one_minus_beta1, fp32(m * beta1))                  mul_ then add_(b, alpha=)
+ *   v'     = fma(fp32(one_minus_beta2 * b), b, fp32(v * beta2))        mul_ then addcmul_(b, b, value=)
+ *   v_hat' = maximum(v_hat, v')                                         NaN if either is NaN (torch.maximum)
+ *   den    = fp32(fp32(sqrt(v_hat') / sqrt_bc2) + eps)
+ *   out    = fp32(g + fp32(fp32(step * m') / den))                      torch.addcdiv: (value * t1) / t2
+ * sqrt_bc2 = (float)sqrt(1 - beta_2 ** round), step = (float)(lr_t / (1 - beta_1 ** round)), both computed in
+ * doubles by the caller, as are one_minus_beta* = (float)(1 - beta_*). m, v and v_hat are updated in place
+ * (plain loads and stores); d_buf and d_g are read non-temporally and d_out is written non-temporally. The
+ * averaged buffer is not written back (fadas.py:75 clears it). The square root is the correctly rounded one:
+ * torch's CPU fp32 sqrt is one ulp low on about 0.6 % of inputs and is not imitated.
+ * Argument errors as adfl_fedbuff_flush_batched. */
+int adfl_fadas_flush_batched(const float* const* d_buf, const float* const* d_g, float* const* d_m,
+                             float* const* d_v, float* const* d_v_hat, float* const* d_out,
+                             const adfl_slq_chunk* d_chunks, int64_t nchunks, int32_t ntensors, int32_t K, float beta1,
+                             float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2, float eps,
+                             float step, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

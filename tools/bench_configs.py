@@ -26,6 +26,11 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             decode launch followed by torch's alpha * g + beta * d on the device (HIP events, Infinity Cache
             flushed); and host to host, receive_axpby against on_server_receive + the reference's CPU
             add_parameters (wall). A parity flag per leg; no threshold
+  flush     the buffered servers' flush on a C3-shaped device dict (256 x 45,662 weights + 256 biases) and on one
+            2^28-element tensor: flush.fedbuff_flush_batched / fadas_flush_batched (one launch) against the
+            reference's statements run by torch on the same device tensors in the same process (FedBuff 4 launches
+            per tensor, FADAS 10); HIP events, Infinity Cache read-flushed before every call, medians of --steps
+            calls, three repeats; parity against the numpy restatement (tests/flush_cases.py); no threshold
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -1127,6 +1132,132 @@ def mode_apply(args, world, rank, dev):
             "steps": args.steps, "c3_equal": c3, "one_tensor": big}
 
 
+def _flush_leg(sizes, args, dev, junk, repeats=3, sample=1 << 20):
+    """One dict of the flush leg: `sizes` separately allocated device tensors. Fused: one launch over pointer
+    tables. Torch: the reference's statements (fed_buff.py:88-92; fadas.py:69-70,105-106,127-129) per tensor on
+    the same device tensors; its in-place `div_` works on a copy of the buffer refreshed before every call, outside
+    the timed span. The moments are updated in place by both legs, each on its own copy. Parity: the fused results
+    of one call from known moments against tests/flush_cases.py, on every element of a tensor of at most `sample`
+    elements and on the first, middle and last `sample` elements of a longer one."""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import flush_cases as fc
+    from adfl_amd import flush, ops
+    K, lr, rnd = 10, 0.05, 3
+    lay = ops.BucketLayout(list(sizes))
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def make(scale, positive=False):
+        ts = [torch.randn(n, device=dev, generator=g) * scale for n in sizes]
+        return [t.abs_() for t in ts] if positive else ts
+
+    buf, gp = make(1e-2), make(1.0)
+    m0, v0 = make(1e-3), make(1e-5, positive=True)
+    h0 = [t * 1.5 for t in v0]
+    out = [torch.empty_like(t) for t in gp]
+    sc = flush.fadas_scalars(0.9, 0.999, 1e-8, lr, rnd)
+
+    def windows(n):
+        if n <= sample:
+            return [(0, n)]
+        return [(0, sample), ((n - sample) // 2, (n - sample) // 2 + sample), (n - sample, n)]
+
+    def host(ts):
+        return [[t[a:b].cpu().numpy() for a, b in windows(t.numel())] for t in ts]
+
+    # parity from known moments
+    mf, vf, hf = ([t.clone() for t in x] for x in (m0, v0, h0))
+    flush.fedbuff_flush_batched(buf, gp, out, lay, K, lr)
+    fb = host(out)
+    flush.fadas_flush_batched(buf, gp, mf, vf, hf, out, lay, K, sc)
+    torch.cuda.synchronize()
+    got = {"m": host(mf), "v": host(vf), "v_hat": host(hf), "out": host(out)}
+    hb, hg, hm, hv, hh = (host(x) for x in (buf, gp, m0, v0, h0))
+    parity_fedbuff = parity_fadas = True
+    checked = 0
+    for t in range(len(sizes)):
+        for w in range(len(hb[t])):
+            parity_fedbuff &= bool(fc.same_bits(fb[t][w], fc.fedbuff_flush(hb[t][w], hg[t][w], K, lr)).all())
+            want = fc.fadas_flush(hb[t][w], hg[t][w], hm[t][w], hv[t][w], hh[t][w], K, sc)
+            parity_fadas &= all(bool(fc.same_bits(got[k][t][w], want[k]).all()) for k in got)
+            checked += hb[t][w].size
+    del fb, got, hb, hg, hm, hv, hh
+
+    work = [torch.empty_like(t) for t in buf]
+    mt, vt, ht = ([t.clone() for t in x] for x in (m0, v0, h0))
+    sqrt_bc2, step = sc[4], sc[6]
+
+    def span(body, refresh=False):
+        def run(ev):
+            if refresh:
+                torch._foreach_copy_(work, buf)
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            body()
+            if ev is not None:
+                ev[1].record()
+        return run
+
+    keep = []
+
+    def torch_fedbuff():
+        with torch.no_grad():
+            for t in work:
+                t.float().div_(K)
+            keep[:] = [(1.0 * a) + (lr * b) for a, b in zip(gp, work)]
+
+    def torch_fadas():
+        with torch.no_grad():
+            for t in work:
+                t.float().div_(K)
+            for b, m, v, h in zip(work, mt, vt, ht):
+                m.mul_(0.9).add_(b, alpha=(1 - 0.9))
+                v.mul_(0.999).addcmul_(b, b, value=(1 - 0.999))
+                torch.maximum(h, v, out=h)
+            res = []
+            for a, m, h in zip(gp, mt, ht):
+                denom = (h.sqrt() / sqrt_bc2).add_(1e-8)
+                res.append(torch.addcdiv(a, m, denom, value=step))
+            keep[:] = res
+
+    legs = {"fedbuff_fused": span(lambda: flush.fedbuff_flush_batched(buf, gp, out, lay, K, lr)),
+            "fedbuff_torch": span(torch_fedbuff, refresh=True),
+            "fadas_fused": span(lambda: flush.fadas_flush_batched(buf, gp, mf, vf, hf, out, lay, K, sc)),
+            "fadas_torch": span(torch_fadas, refresh=True)}
+    ms = {k: [] for k in legs}
+    for _ in range(repeats):   # the four legs alternate within a repeat
+        for k, step_fn in legs.items():
+            _, evs = timed(step_fn, args.steps, args.warmup, 1, 2)
+            ms[k].append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+    del keep[:]
+    n = int(sum(sizes))
+    res = {"tensors": len(sizes), "elements": n, "parity_elements": checked, "parity_fedbuff": parity_fedbuff,
+           "parity_fadas": parity_fadas, "K": K, "round": rnd}
+    for k, v in ms.items():
+        res[k + "_ms"] = [round(x, 4) for x in v]
+    for name, nbytes in (("fedbuff", 12), ("fadas", 36)):
+        f, t = _median(ms[name + "_fused"]), _median(ms[name + "_torch"])
+        res[name + "_ratio"] = round(t / f, 3)
+        res[name + "_fused_frac_moved"] = round(nbytes * n / (f * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    return res
+
+
+def mode_flush(args, world, rank, dev):
+    """The buffered servers' flush: one fused launch against the reference's statements run by torch on the same
+    device tensors. No threshold and no parent-commit number (the path is new): times, ratios, parity flags."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    c3 = _flush_leg(list(recipes.bucket_sizes("equal")) + [64] * 256, args, dev, junk)
+    big = _flush_leg([args.elems or 1 << 28], args, dev, junk)
+    return {"mode": "flush", "metric": "FADAS flush (m, v, v_hat in place + params_prime), C3-shaped device dict, one "
+            "launch, Infinity Cache flushed", "unit": "ms", "value": _median(c3["fadas_fused_ms"]),
+            "parity": all(leg[f] for leg in (c3, big) for f in ("parity_fedbuff", "parity_fadas")),
+            "steps": args.steps, "repeats": 3, "c3_dict": c3, "one_tensor": big}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1134,7 +1265,7 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta", "delta_stoch", "apply"], required=True)
+                                      "delta", "delta_stoch", "apply", "flush"], required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -1151,7 +1282,8 @@ def main():
     dev = torch.device("cuda", local)
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
-            "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply}[args.mode](
+            "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
+            "flush": mode_flush}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
