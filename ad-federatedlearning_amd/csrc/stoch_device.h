@@ -112,7 +112,11 @@ __device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b, uint32_t c, ui
 // r = RN(a - b*q) (exact), q' = RN(q + r*y) = RN(a/b) while every intermediate stays normal; it is valid
 // for b in [2^-60, 2^60] (block-uniform) and |a| in {0} U [2^-60, 2^60]. 4.4 vs 12.1 lane-cycles per
 // quotient, and 0 of 1.7e10 random operand pairs differ from __fdiv_rn (tools/microbench_stoch.hip,
-// profiles/r01/microbench_stoch.txt).
+// profiles/r01/microbench_stoch.txt). That count is evidence; what guards the window, the flags and the ballot is
+// tests/test_gpu_stoch_boundary.py on the inputs of tests/boundary_cases.py: scaled on every integer and one ulp
+// to either side, u == prob, both window edges, waves with only some lanes flagged, and the reason for 2^60 —
+// 2^-60 / 2^60 keeps the quotient normal; a denormal quotient can be an exact tie, which q' rounds by the sign of
+// y's error instead of to even (the fixture's `tie` elements differ with the window at 2^+-70).
 struct Div {
   float b, y;
   bool fast;
