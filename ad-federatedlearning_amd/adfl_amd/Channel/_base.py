@@ -213,6 +213,24 @@ class _CodecChannel(Channel):
                         t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
         return time.perf_counter() - s_time
 
+    def broadcast_delta_(self, hidden_state: Parameters,
+                         params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """QAFeL's broadcast (Src/ADFL/Server/qafel.py:156-180): ``_broadcast_update``'s encode and
+        ``_update_hidden_state`` in one call. Returns (c_params, seconds):
+
+        * c_params equals ``on_server_send(diff_parameters(hidden_state, params_new))[0]`` field for field, in
+          hidden_state's key order, and the same errors are raised (send_delta's);
+        * afterwards hidden_state holds what ``add_parameters_inpace(hidden_state,
+          on_client_receive(c_params)[0], 1, 1, False)`` leaves: updated in place, the same tensor objects;
+        * params_new is not modified.
+
+        Here: ``send_delta`` then ``receive_add_(c_params, [hidden_state])``, drawing the one random stream that
+        pair draws. The SLQ channels fuse the two on a device-resident hidden state (quant.py)."""
+        s_time = time.perf_counter()
+        c_params, _ = self.send_delta(hidden_state, params_new)
+        self.receive_add_(c_params, [hidden_state])
+        return c_params, time.perf_counter() - s_time
+
     def receive_mean(self, all_c_params: List[CompressedParameters]) -> Tuple[Parameters, float]:
         """``simple_aggregate([self.on_server_receive(c)[0] for c in all_c_params])`` — a synchronous
         server decoding K client updates and averaging them (Src/ADFL/Strategy/simple.py:83-89 over
@@ -429,6 +447,21 @@ class _Unidirectional:
 
     def on_client_receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
         return IdentityChannel(no_compute_time=True).on_client_receive(c_params)
+
+    def broadcast_delta_(self, hidden_state: Parameters,
+                         params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """The server -> client direction is the identity channel, so there is nothing to encode or fuse: the
+        reference's four statements (Src/ADFL/Server/qafel.py:160-161,179-180 over model.py:337-358)."""
+        s_time = time.perf_counter()
+        assert set(hidden_state.keys()) == set(params_new.keys())            # diff_parameters, model.py:352
+        with torch.no_grad():
+            update = {k: params_new[k] - hidden_state[k] for k in hidden_state}
+            q_update, _ = self.on_server_send(update)
+            d_update, _ = self.on_client_receive(q_update)
+            assert set(hidden_state.keys()) == set(d_update.keys())          # add_parameters_inpace, model.py:340
+            for k in d_update:
+                hidden_state[k].mul_(1).add_(d_update[k].to(hidden_state[k].device), alpha=1)
+        return q_update, time.perf_counter() - s_time
 
 
 def _delta_on_device(prevs: List[torch.Tensor], news: List[torch.Tensor], dev: torch.device):

@@ -566,6 +566,68 @@ def _encode_delta_dict_packed(prevs: List[torch.Tensor], news: List[torch.Tensor
     return _packed_out(names, news, lay, st, p_dev, s_dev, host_ok, numel)
 
 
+def _broadcast_groups(params_prev: Parameters, pairs, dev: torch.device):
+    """broadcast_delta_'s fused entries as [names], one list per placement of params_new (on the staging device,
+    on the CPU). An ndim > 1 pair (hidden, new) — fp32, of one shape and non-empty: _delta_pairs saw to that — is
+    fused when the hidden tensor is the caller's own, contiguous and on the staging device, `new` is contiguous
+    there or anywhere on the CPU, and the two do not share storage. Every other pair takes send_delta's encode
+    and receive_add_'s update."""
+    on_dev: List[str] = []
+    on_cpu: List[str] = []
+    for n, (h, g) in pairs.items():
+        if (h is not params_prev[n] or not h.is_cuda or h.device != dev or not h.is_contiguous()
+                or h.dtype != torch.float32 or g.dtype != torch.float32):
+            continue
+        if g.is_cuda:
+            if (g.device == dev and g.is_contiguous()
+                    and g.untyped_storage().data_ptr() != h.untyped_storage().data_ptr()):
+                on_dev.append(n)
+        elif g.device.type == "cpu":
+            on_cpu.append(n)
+    return [g for g in (on_dev, on_cpu) if g]
+
+
+@_serialized
+def _encode_delta_update_dict(hiddens: List[torch.Tensor], news: List[torch.Tensor], names: List[str], bits: int,
+                              packed: bool):
+    """SLQ-encode news[k] - hiddens[k] and, in the same launch, hiddens[k] += decode(payload) (_broadcast_groups'
+    entries; ops.encode_delta_update_batched): the payloads of _encode_delta_dict (packed: _encode_delta_dict_packed)
+    for the same pair, on news[k]'s device.
+
+    The hidden tensors are read and written where they are, through their pointer table. `news` on the device:
+    a second pointer table, nothing staged. `news` on the CPU (get_model_parameters hands out CPU dicts): staged
+    into a 64-element-aligned bucket by one H2D copy. Either way the payload goes to a 64-element-aligned bucket
+    and from there into the owned outputs: one scatter launch on the device, the D2H + scatter path on the CPU."""
+    st = _staging()
+    dev = st.device
+    th = _torchhost.get()
+    host_ok, numel, hptrs = th.host_bytes(news, 4)   # sizes, and contiguous CPU fp32 storages, in one call
+    lay = st.layout(tuple(numel.tolist()), align=ops.ALIGN_ELEMS)
+    ok_h, _, h_ptrs = th.device_ptrs(hiddens, dev.index, 4)
+    if not ok_h:
+        raise ValueError("broadcast_delta_: the fused hidden tensors must be contiguous fp32 tensors on the device")
+    if news[0].is_cuda:
+        ok_n, _, n_ptrs = th.device_ptrs(news, dev.index, 4)
+        if not ok_n:
+            raise ValueError("broadcast_delta_: the fused new tensors must be contiguous fp32 tensors on the device")
+    else:
+        x_dev = _stage_in(news, lay, st, "x", torch.float32,
+                          host_ptrs=hptrs.numpy().view(np.uint64) if host_ok else None)
+        n_ptrs = torch.from_numpy(x_dev.data_ptr() + 4 * lay.offsets)
+    scales = st.buf("scales", lay.ntensors, torch.float32)
+    partials = st.buf("partials", lay.nchunks, torch.int32)
+    with torch.no_grad():
+        if packed:
+            p_dev, s_dev = ops.encode_delta_update_batched_int4(news, hiddens, lay, bits, ptrs=(n_ptrs, h_ptrs),
+                                                                packed=st.buf("p", lay.total // 2, torch.uint8),
+                                                                scales=scales, partials=partials)
+            return _packed_out(names, news, lay, st, p_dev, s_dev, host_ok, numel)
+        q_dev, s_dev = ops.encode_delta_update_batched(news, hiddens, lay, bits, ptrs=(n_ptrs, h_ptrs),
+                                                       q=st.buf("q", lay.total, torch.int8), scales=scales,
+                                                       partials=partials)
+        return _payloads_out(names, news, lay, st, q_dev, s_dev)
+
+
 class SLQChannel(_CodecChannel):
     """Bi-directional symmetric linear quantization (quant.py:15-112) on the MI355X HIP codec:
     ``simulate_bandwidth`` counts self.bits for weights, 32 bits for biases, 32 bits per scale (quant.py:47-58).
@@ -704,11 +766,47 @@ class SLQChannel(_CodecChannel):
         q_params = self._quantize_delta(params_prev, params_new, self.bits)
         return q_params, time.perf_counter() - s_time
 
-    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int) -> QuantParameters:
+    def broadcast_delta_(self, hidden_state: Parameters,
+                         params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``_CodecChannel.broadcast_delta_`` (QAFeL's broadcast: send_delta(hidden_state, params_new), then
+        receive_add_(c_params, [hidden_state])) with the two fused for a device-resident hidden state: the ndim > 1
+        entries ``_broadcast_groups`` names are encoded and their hidden tensors updated by the same launch
+        (ops.encode_delta_update_batched: read g, read h, write the payload, write h — the payload never comes
+        back in), whether params_new is on the device (pointer tables, nothing staged) or on the CPU (staged by
+        one H2D copy). The payload tensors live where params_new's do, as with send_delta. ndim <= 1 entries
+        keep torch's own statements (``new - prev`` with scale 1, then ``mul_(1).add_``); a CPU hidden state and
+        every other entry take send_delta's encode and receive_add_'s update."""
+        s_time = time.perf_counter()
+        q_params = self._quantize_delta(hidden_state, params_new, self.bits, update=True)
+        return q_params, time.perf_counter() - s_time
+
+    _PACKED_DELTA = False   # PackedSLQChannel: the int4-packed delta encodes
+
+    def _encode_delta_pairs(self, params_prev: Parameters, pairs, bits: int, update: bool):
+        """({name: (payload, scale)} of _delta_pairs' ndim > 1 pairs, the names whose params_prev tensor the
+        encode has already updated: broadcast_delta_'s fused entries, none without `update`)."""
+        encoded: Dict[str, Tuple[torch.Tensor, float]] = {}
+        if update and pairs:
+            for grp in _broadcast_groups(params_prev, pairs, _staging().device):
+                encoded.update(_encode_delta_update_dict([pairs[n][0] for n in grp], [pairs[n][1] for n in grp], grp,
+                                                         bits, self._PACKED_DELTA))
+        done = set(encoded)
+        rest = [n for n in pairs if n not in done]
+        if rest:
+            enc = _encode_delta_dict_packed if self._PACKED_DELTA else _encode_delta_dict
+            encoded.update(enc([pairs[n][0] for n in rest], [pairs[n][1] for n in rest], rest, bits))
+        return encoded, done
+
+    def _update_rest(self, params_prev: Parameters, out: Dict[str, QuantParameter], done) -> None:
+        """broadcast_delta_'s entries the fused launch did not take: receive_add_ of their payloads."""
+        rest = {n: p for n, p in out.items() if n not in done}
+        if rest:
+            self.receive_add_(QuantParameters(rest, 0), [{n: params_prev[n] for n in rest}])
+
+    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int,
+                        update: bool = False) -> QuantParameters:
         names, plain, pairs = _delta_pairs(params_prev, params_new)
-        qnames = list(pairs)
-        encoded = _encode_delta_dict([pairs[n][0] for n in qnames], [pairs[n][1] for n in qnames], qnames,
-                                     bits) if qnames else {}
+        encoded, done = self._encode_delta_pairs(params_prev, pairs, bits, update)
         signs = torch.zeros(1, dtype=torch.uint8)  # the unused field (quant.py:91), one object per call
         qp = QuantParameter
         out: Dict[str, QuantParameter] = {}
@@ -723,6 +821,8 @@ class SLQChannel(_CodecChannel):
                 t = plain[n]                  # passthrough (quant.py:80-81: scale 1)
                 out[n] = qp(t, bits, 1, signs, t.shape, t.dtype, t.dtype)
                 size += t.nbytes
+        if update:
+            self._update_rest(params_prev, out, done)
         return QuantParameters(out, size)
 
     def _quantize_params(self, params: Parameters, bits: int, stats: Optional[list] = None) -> QuantParameters:
@@ -823,11 +923,12 @@ class PackedSLQChannel(SLQChannel):
                             [[c.params[n].scale for n in names] for c in all_c_params],
                             [torch.Size(all_c_params[0].params[n].shape) for n in names], packed=True)
 
-    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int) -> QuantParameters:
+    _PACKED_DELTA = True
+
+    def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int,
+                        update: bool = False) -> QuantParameters:
         names, plain, pairs = _delta_pairs(params_prev, params_new)
-        qnames = list(pairs)
-        encoded = _encode_delta_dict_packed([pairs[n][0] for n in qnames], [pairs[n][1] for n in qnames], qnames,
-                                            bits) if qnames else {}
+        encoded, done = self._encode_delta_pairs(params_prev, pairs, bits, update)
         signs = torch.zeros(1, dtype=torch.uint8)  # the unused field (compression.py:102), one object per call
         qp = QuantParameter
         out: Dict[str, QuantParameter] = {}
@@ -841,6 +942,8 @@ class PackedSLQChannel(SLQChannel):
                 shape, dtype = q_param.shape, q_param.dtype
             out[n] = qp(q_param, bits, scale, signs, shape, dtype, q_param.dtype)
             size += q_param.nbytes
+        if update:
+            self._update_rest(params_prev, out, done)
         return QuantParameters(out, size)
 
     def _quantize_params(self, params: Parameters, bits: int, stats: Optional[list] = None) -> QuantParameters:

@@ -78,6 +78,10 @@ SIGNATURES = {
     "adfl_slq_encode_delta_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
     "adfl_slq_encode_delta_batched_int4": (INT, [P, P, P, I64, INT, P, P, P, P]),
     "adfl_slq_encode_delta_batched_int4_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_update_batched": (INT, [P, P, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_update_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_update_batched_int4": (INT, [P, P, P, I64, INT, P, P, P, P]),
+    "adfl_slq_encode_delta_update_batched_int4_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
     # adfl_stoch.h
     "adfl_stoch_workspace_bytes": (I64, [I64]),
     "adfl_stoch_norms_batched": (INT, [P, P, I64, INT, P, I64, P, P, P]),

@@ -710,6 +710,72 @@ def encode_delta_batched_int4(new, prev, layout: BucketLayout, bits: int = 4, *,
     return packed, scales
 
 
+# Delta encode + hidden-state update over a resident-eligible layout: "resident" (one launch, h re-read tile by
+# tile) or "twopass" (absmax launch + fused quantize/update launch). Every other layout takes the two passes.
+# ADFL_SLQ_ENCODE=twopass forces them, as for the other encodes. DESIGN.md §9 item 8 has the measurement.
+_UPDATE_RESIDENT_FORM = "resident"
+
+
+def _update_nwork(layout: BucketLayout) -> int:
+    return _delta_nwork(layout) if _UPDATE_RESIDENT_FORM == "resident" else 0
+
+
+def _update_tables(new, hidden, layout: BucketLayout, ptrs, what: str):
+    """(device, *_delta_tables) for (new, hidden), after checking that `hidden` can be written in place: a flat
+    fp32 device buffer that is contiguous as given (a copy would take the update), or a list of fp32 device
+    tensors (which _delta_sources requires to be contiguous). The device is hidden's: with `ptrs`, `new` may be
+    a list of CPU tensors the caller has staged."""
+    if ptrs is None and isinstance(hidden, torch.Tensor):
+        if hidden.dtype != torch.float32 or not hidden.is_cuda or not hidden.is_contiguous():
+            raise ValueError(f"{what}: hidden must be a contiguous fp32 device buffer (it is updated in place), got "
+                             f"{hidden.dtype} on {hidden.device}")
+    elif ptrs is None:
+        for t, x in enumerate(hidden):
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda:
+                raise ValueError(f"{what}: hidden[{t}] must be an fp32 device tensor (it is updated in place)")
+    dev = _delta_device(hidden, new)
+    return (dev,) + _delta_tables(new, hidden, layout, dev, ptrs)
+
+
+def encode_delta_update_batched(new, hidden, layout: BucketLayout, bits: int, *, q: Optional[torch.Tensor] = None,
+                                scales: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None,
+                                ptrs=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """QAFeL's broadcast (Src/ADFL/Server/qafel.py:156-180) in one pass: ``encode_delta_batched(new, hidden)``
+    and, in place, ``hidden += decode(payload)`` — per element fp32(h + fp32(scale * code)), two rounded
+    operations, bit-identical to encode_delta_batched followed by dequantize_add_batched into `hidden`.
+    Sources as encode_delta_batched takes them; `hidden` must be writable fp32 on the device (a contiguous flat
+    buffer, or a list of contiguous tensors), must not overlap `new`, and is the only thing modified besides the
+    outputs. Returns (int8 payload bucket in `layout`, per-tensor fp32 scales). ptrs: see _delta_tables."""
+    dev, n_tab, h_tab, _keep = _update_tables(new, hidden, layout, ptrs, "encode_delta_update_batched")
+    q = _dst(q, layout.total, torch.int8, dev, "q")
+    scales = _dst(scales, layout.ntensors, torch.float32, dev, "scales", align=4)
+    partials = _dst(partials, layout.nchunks, torch.int32, dev, "partials", align=4)
+    check(_lib.load().adfl_slq_encode_delta_update_batched_work(
+        n_tab.data_ptr(), h_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        layout.device_work(dev).data_ptr(), _update_nwork(layout), bits, q.data_ptr(), scales.data_ptr(),
+        partials.data_ptr(), _stream(dev)))
+    return q, scales
+
+
+def encode_delta_update_batched_int4(new, hidden, layout: BucketLayout, bits: int = 4, *,
+                                     packed: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
+                                     partials: Optional[torch.Tensor] = None,
+                                     ptrs=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """encode_delta_update_batched with the int4-packed payload of encode_delta_batched_int4 (even tensor
+    offsets): `hidden` takes what the packed bytes decode to — nibble - 8 read back from each byte, so the codes
+    127 of an all-equal or NaN tensor alias as pack_4bit makes them, and an odd tensor's pad is a zero code."""
+    _require_even_offsets(layout)
+    dev, n_tab, h_tab, _keep = _update_tables(new, hidden, layout, ptrs, "encode_delta_update_batched_int4")
+    packed = _dst(packed, (layout.total + 1) // 2, torch.uint8, dev, "packed")
+    scales = _dst(scales, layout.ntensors, torch.float32, dev, "scales", align=4)
+    partials = _dst(partials, layout.nchunks, torch.int32, dev, "partials", align=4)
+    check(_lib.load().adfl_slq_encode_delta_update_batched_int4_work(
+        n_tab.data_ptr(), h_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        layout.device_work(dev).data_ptr(), _update_nwork(layout), bits, packed.data_ptr(), scales.data_ptr(),
+        partials.data_ptr(), _stream(dev)))
+    return packed, scales
+
+
 def bucket_diff(new, prev, layout: BucketLayout, *, out: Optional[torch.Tensor] = None, ptrs=None) -> torch.Tensor:
     """``new - prev`` of every tensor as one flat fp32 bucket in `layout`, one launch (adfl_bucket_diff): torch's
     own subtraction bit for bit, written once — the stochastic DELTA route of the codecs whose scale is the
@@ -1028,3 +1094,51 @@ def slq_decode_axpby_batched_int4_op(packed: torch.Tensor, scales: torch.Tensor,
 @slq_decode_axpby_batched_int4_op.register_fake
 def _(packed, scales, base, offsets, sizes, alpha, beta):
     return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
+def _update_flat(new: torch.Tensor, hidden: torch.Tensor, lay: BucketLayout, what: str):
+    """The two flat buckets of a broadcast op: `hidden` is updated in place, so it is taken as it is (a
+    contiguous fp32 device buffer), never copied."""
+    if hidden.dtype != torch.float32 or not hidden.is_contiguous():
+        raise ValueError(f"{what}: hidden must be a contiguous float32 bucket (it is updated in place), got "
+                         f"{hidden.dtype}")
+    new, hidden = new.reshape(-1), hidden.view(-1)
+    if new.numel() < lay.total or hidden.numel() < lay.total:
+        raise ValueError(f"{what}: flat buffer smaller than the layout")
+    return new, hidden
+
+
+# QAFeL's broadcast (torch.ops.adfl_apply.*, beside the other server steps; torch.ops.adfl.* is the codec proper).
+@torch.library.custom_op("adfl_apply::slq_encode_delta_update_batched", mutates_args=("hidden",))
+def slq_encode_delta_update_batched_op(new: torch.Tensor, hidden: torch.Tensor, offsets: torch.Tensor,
+                                       sizes: torch.Tensor, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """slq_encode_delta_batched(new, hidden), and in place hidden += decode(payload): fp32(h + fp32(scale *
+    code)) per element of every tensor of the caller-placed layout; positions no tensor owns are untouched."""
+    lay = layout_for(offsets, sizes)
+    new, hidden = _update_flat(new, hidden, lay, "slq_encode_delta_update_batched")
+    q = _filled(new.numel(), torch.int8, new.device, lay)
+    return encode_delta_update_batched(new, hidden, lay, bits, q=q)
+
+
+@slq_encode_delta_update_batched_op.register_fake
+def _(new, hidden, offsets, sizes, bits):
+    return new.new_empty((new.numel(),), dtype=torch.int8), new.new_empty((sizes.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_encode_delta_update_batched_int4", mutates_args=("hidden",))
+def slq_encode_delta_update_batched_int4_op(new: torch.Tensor, hidden: torch.Tensor, offsets: torch.Tensor,
+                                            sizes: torch.Tensor, bits: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """slq_encode_delta_update_batched with the int4-packed payload (even tensor offsets): hidden takes what the
+    packed bytes decode to."""
+    lay = layout_for(offsets, sizes)
+    new, hidden = _update_flat(new, hidden, lay, "slq_encode_delta_update_batched_int4")
+    nbytes = (new.numel() + 1) // 2
+    gap = int(lay.sizes.sum()) != new.numel()
+    packed = (torch.zeros if gap else torch.empty)(nbytes, dtype=torch.uint8, device=new.device)
+    return encode_delta_update_batched_int4(new, hidden, lay, bits, packed=packed)
+
+
+@slq_encode_delta_update_batched_int4_op.register_fake
+def _(new, hidden, offsets, sizes, bits):
+    return (new.new_empty(((new.numel() + 1) // 2,), dtype=torch.uint8),
+            new.new_empty((sizes.numel(),), dtype=torch.float32))

@@ -300,6 +300,42 @@ int adfl_slq_encode_delta_batched_int4_work(const float* const* d_new, const flo
                                             int64_t nwork, int bits, uint8_t* d_packed, float* d_scales,
                                             uint32_t* d_partials, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Delta encode + hidden-state update — QAFeL's broadcast (Src/ADFL/Server/qafel.py:156-180):
+ *   q = encode(g - h) ; h += decode(q)
+ * in one pass over g (d_new) and h (d_hidden). Additions: ADFL_SLQ_ABI_VERSION is unchanged.
+ * The payload, scales and partials are exactly those of adfl_slq_encode_delta_batched*(d_new, d_hidden, ...).
+ * Then, with c the code the decode reads back from the stored bytes (int8: the code; int4: nibble - 8 of the
+ * packed byte, so an out-of-range code 127 aliases as pack_4bit makes it and an odd tensor's pad is a zero
+ * code), per element
+ *   h'[i] = fp32(h[i] + fp32(scale * c[i]))
+ * two separately rounded fp32 operations, never an FMA: what adfl_slq_dequantize_add_batched computes on that
+ * payload. No special cases: an all-equal tensor (scale 0, codes 127) adds +-0; a NaN anywhere makes the scale
+ * and the tensor's whole hidden state NaN; an inf makes the scale inf and inf * 0 = NaN on the finite elements.
+ * d_new is never written; d_hidden[t] is written in place, once per element; nothing outside the tensors'
+ * elements is written. d_new[t] overlapping d_hidden[t], or two tensors of d_hidden overlapping, is undefined.
+ * Arguments, alignment rule (the three addresses at the element where the payload reaches a 16-byte boundary
+ * decide between the 16-byte path and the element-wise one, per block) and error codes are those of the delta
+ * entries above; nothing is launched on an error. The _work forms are the one-launch form over the work list
+ * of adfl_slq_build_encode_work (nwork == 0: the two passes): the block holds the difference in registers and
+ * re-reads h tile by tile for the update. A work list entry naming a tensor of more than
+ * ADFL_SLQ_DELTA_RESIDENT_CHUNKS chunks gets a NaN scale, no payload and an untouched h.
+ * ------------------------------------------------------------------------------------------- */
+int adfl_slq_encode_delta_update_batched(const float* const* d_new, float* const* d_hidden,
+                                         const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits, int8_t* d_q,
+                                         float* d_scales, uint32_t* d_partials, void* stream);
+int adfl_slq_encode_delta_update_batched_work(const float* const* d_new, float* const* d_hidden,
+                                              const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                              int64_t nwork, int bits, int8_t* d_q, float* d_scales,
+                                              uint32_t* d_partials, void* stream);
+int adfl_slq_encode_delta_update_batched_int4(const float* const* d_new, float* const* d_hidden,
+                                              const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                              uint8_t* d_packed, float* d_scales, uint32_t* d_partials, void* stream);
+int adfl_slq_encode_delta_update_batched_int4_work(const float* const* d_new, float* const* d_hidden,
+                                                   const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                                   const int32_t* d_work, int64_t nwork, int bits, uint8_t* d_packed,
+                                                   float* d_scales, uint32_t* d_partials, void* stream);
+
 /* Device staging of a state dict as one bucket (the gather / scatter around every bucketed entry above when
  * the dict's tensors live on the device; the reference's per-tensor loop, quant.py:67-94, has one tensor per
  * op): every tensor's elements copied between its own storage and its slot of the bucket, one launch for the

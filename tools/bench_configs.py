@@ -1258,6 +1258,150 @@ def mode_flush(args, world, rank, dev):
             "steps": args.steps, "repeats": 3, "c3_dict": c3, "one_tensor": big}
 
 
+def _broadcast_leg(sizes, args, dev, junk, repeats=3):
+    """One layout of the broadcast leg, hidden state and g both device-resident. Kernels alone (HIP events, the
+    Infinity Cache read-flushed before every call): ops.encode_delta_batched followed by ops.dequantize_add_batched
+    (the pair the fused launch replaces) against ops.encode_delta_update_batched in its two-pass form and, where
+    the layout allows it, its resident form. Whole call (wall): broadcast_delta_ against send_delta + receive_add_.
+    Every figure is `repeats` medians of args.steps calls, all listed; a fused form counts as faster when its
+    worst repeat is below the pair's best repeat (the gap exceeds the spread of the repeats)."""
+    from adfl_amd import _lib, ops
+    from adfl_amd.Channel import SLQChannel
+    gen = torch.Generator(device=dev).manual_seed(0)
+    hidden, new = {}, {}
+    for i, n in enumerate(sizes):
+        for name, shape in ((f"layer{i:03d}.weight", (1, n)), (f"layer{i:03d}.bias", (64,))):
+            new[name] = torch.randn(shape, device=dev, generator=gen) * 1e-2
+            hidden[name] = new[name] + torch.randn(shape, device=dev, generator=gen) * 1e-5
+    names = [k for k in hidden if hidden[k].ndim > 1]
+    gs, hs = [new[k] for k in names], [hidden[k] for k in names]
+    lay = ops.BucketLayout(list(sizes))
+    ptrs = tuple(torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64) for ts in (gs, hs))
+    q = torch.empty(lay.total, dtype=torch.int8, device=dev)
+    scales = torch.empty(lay.ntensors, device=dev)
+    partials = torch.empty(lay.nchunks, dtype=torch.int32, device=dev)
+    resident_ok = lay.nwork > 0 and lay.max_tensor_chunks <= _lib.DELTA_RESIDENT_CHUNKS
+    n = int(sum(sizes))
+
+    # parity of each fused form against the pair, on copies
+    def pair_on(h):
+        qq, ss = ops.encode_delta_batched(gs, h, lay, 8)
+        ops.dequantize_add_batched(qq, ss, lay, [h])
+        return qq, ss
+    want_h = [t.clone() for t in hs]
+    want_q, want_s = pair_on(want_h)
+    parity = {}
+    for form in (("twopass", "resident") if resident_ok else ("twopass",)):
+        ops._UPDATE_RESIDENT_FORM = form
+        got_h = [t.clone() for t in hs]
+        got_q, got_s = ops.encode_delta_update_batched(gs, got_h, lay, 8)
+        owned = torch.zeros(lay.total, dtype=torch.bool, device=dev)
+        for o, m in zip(lay.offsets.tolist(), sizes):
+            owned[o:o + m] = True
+        parity[form] = bool(torch.equal(got_q[owned], want_q[owned])
+                            and torch.equal(got_s.view(torch.int32), want_s.view(torch.int32))
+                            and all(torch.equal(a.view(torch.int32), b.view(torch.int32))
+                                    for a, b in zip(got_h, want_h)))
+    del want_h, want_q, got_h, got_q
+
+    def k_pair(ev):
+        junk.amax()   # read-flush of the Infinity Cache
+        if ev is not None:
+            ev[0].record()
+        ops.encode_delta_batched(gs, hs, lay, 8, q=q, scales=scales, partials=partials, ptrs=ptrs)
+        ops.dequantize_add_batched(q, scales, lay, [hs])
+        if ev is not None:
+            ev[1].record()
+
+    def k_fused(ev):
+        junk.amax()
+        if ev is not None:
+            ev[0].record()
+        ops.encode_delta_update_batched(gs, hs, lay, 8, q=q, scales=scales, partials=partials, ptrs=ptrs)
+        if ev is not None:
+            ev[1].record()
+
+    def events(step):
+        out = []
+        for _ in range(repeats):
+            _, evs = timed(step, args.steps, args.warmup, 1, 2)
+            out.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+        return out
+
+    res = {"tensors": len(sizes), "elements": n, "parity": parity}
+    pair = events(k_pair)
+    res["pair_alone_ms"] = round(_median(pair), 4)
+    res["pair_alone_ms_repeats"] = [round(v, 4) for v in pair]
+    for form in parity:
+        ops._UPDATE_RESIDENT_FORM = form
+        f = events(k_fused)
+        res[f"fused_{form}_alone_ms"] = round(_median(f), 4)
+        res[f"fused_{form}_alone_ms_repeats"] = [round(v, 4) for v in f]
+        res[f"fused_{form}_below_pair_by_more_than_spread"] = bool(max(f) < min(pair))
+        res[f"fused_{form}_over_pair"] = round(_median(f) / _median(pair), 4)
+        # 13 B per element: read g, read h, write the payload, write h (the two passes read g and h once more)
+        res[f"fused_{form}_frac_of_peak_on_13B"] = round(13 * n / (_median(f) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    ops._UPDATE_RESIDENT_FORM = "resident"
+
+    # the whole call, wall clock
+    ch = SLQChannel(8)
+
+    def wall(fn):
+        out = []
+        for _ in range(args.steps):
+            junk.amax()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return _median(out)
+
+    def two_calls(h):
+        c = ch.send_delta(h, new)[0]
+        ch.receive_add_(c, [h])
+        return c
+    h_a, h_b = ({k: v.clone() for k, v in hidden.items()} for _ in range(2))
+    c_a, c_b = ch.broadcast_delta_(h_a, new)[0], two_calls(h_b)
+    res["call_parity"] = bool(_delta_same(c_a, c_b) and all(
+        torch.equal(h_a[k].view(torch.int32), h_b[k].view(torch.int32)) for k in h_a))
+    del c_a, c_b
+    for _ in range(args.warmup):
+        ch.broadcast_delta_(h_a, new), two_calls(h_b)
+    f_ms = [wall(lambda: ch.broadcast_delta_(h_a, new)) for _ in range(repeats)]
+    u_ms = [wall(lambda: two_calls(h_b)) for _ in range(repeats)]
+    res.update({"broadcast_delta_ms": round(_median(f_ms), 4), "broadcast_delta_ms_repeats": [round(v, 4) for v in f_ms],
+                "send_delta_receive_add_ms": round(_median(u_ms), 4),
+                "send_delta_receive_add_ms_repeats": [round(v, 4) for v in u_ms],
+                "call_below_two_calls_by_more_than_spread": bool(max(f_ms) < min(u_ms))})
+    return res
+
+
+def mode_broadcast(args, world, rank, dev):
+    """QAFeL's broadcast (delta encode + hidden-state update in one launch) against the two calls it replaces, on
+    the C3 layouts and one 2^28-element tensor; written to profiles/broadcast/broadcast.json (an A/B library
+    selected with ADFL_LIB_VARIANT writes broadcast_<its name>.json)."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    legs = {"c3_equal": _broadcast_leg(recipes.bucket_sizes("equal"), args, dev, junk),
+            "c3_loguniform": _broadcast_leg(recipes.bucket_sizes("loguniform", 0), args, dev, junk),
+            "one_tensor_2p28": _broadcast_leg([1 << 28], args, dev, junk)}
+    variant = os.environ.get("ADFL_LIB_VARIANT")
+    line = {"mode": "broadcast", "metric": "fused delta encode + hidden-state update, kernels alone, C3 equal layout, "
+            "Infinity Cache flushed", "unit": "ms", "library": os.path.basename(variant) if variant else "product",
+            "value": min(v for k, v in legs["c3_equal"].items() if k.startswith("fused_") and k.endswith("_alone_ms")),
+            "parity": all(all(leg["parity"].values()) and leg["call_parity"] for leg in legs.values()),
+            "steps": args.steps, "repeats": 3, **legs}
+    out_dir = os.path.join(REPO, "profiles", "broadcast")
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if not variant else "_" + os.path.splitext(os.path.basename(variant))[0].replace("libadfl_", "")
+    with open(os.path.join(out_dir, f"broadcast{tag}.json"), "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    return line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1265,7 +1409,7 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta", "delta_stoch", "apply", "flush"], required=True)
+                                      "delta", "delta_stoch", "apply", "flush", "broadcast"], required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -1283,7 +1427,7 @@ def main():
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
-            "flush": mode_flush}[args.mode](
+            "flush": mode_flush, "broadcast": mode_broadcast}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
