@@ -225,7 +225,8 @@ class _CodecChannel(Channel):
         * params_new is not modified.
 
         Here: ``send_delta`` then ``receive_add_(c_params, [hidden_state])``, drawing the one random stream that
-        pair draws. The SLQ channels fuse the two on a device-resident hidden state (quant.py)."""
+        pair draws. The SLQ channels (quant.py) and the stochastic channels (stoch.py) fuse the two on a
+        device-resident hidden state."""
         s_time = time.perf_counter()
         c_params, _ = self.send_delta(hidden_state, params_new)
         self.receive_add_(c_params, [hidden_state])
@@ -474,6 +475,27 @@ def _delta_on_device(prevs: List[torch.Tensor], news: List[torch.Tensor], dev: t
         return None
     ok_p, _, p_ptrs = th.device_ptrs(prevs, dev.index, 4)
     return (n_ptrs, p_ptrs) if ok_p else None
+
+
+def _broadcast_groups(params_prev: Parameters, pairs, dev: torch.device):
+    """broadcast_delta_'s fused entries as [names], one list per placement of params_new (on the staging device,
+    on the CPU). An ndim > 1 pair (hidden, new) — fp32, of one shape and non-empty: _delta_pairs saw to that — is
+    fused when the hidden tensor is the caller's own, contiguous and on the staging device, `new` is contiguous
+    there or anywhere on the CPU, and the two do not share storage. Every other pair takes send_delta's encode
+    and receive_add_'s update."""
+    on_dev: List[str] = []
+    on_cpu: List[str] = []
+    for n, (h, g) in pairs.items():
+        if (h is not params_prev[n] or not h.is_cuda or h.device != dev or not h.is_contiguous()
+                or h.dtype != torch.float32 or g.dtype != torch.float32):
+            continue
+        if g.is_cuda:
+            if (g.device == dev and g.is_contiguous()
+                    and g.untyped_storage().data_ptr() != h.untyped_storage().data_ptr()):
+                on_dev.append(n)
+        elif g.device.type == "cpu":
+            on_cpu.append(n)
+    return [g for g in (on_dev, on_cpu) if g]
 
 
 def _delta_pairs(params_prev: Parameters, params_new: Parameters, codable=None):

@@ -37,7 +37,7 @@ from .. import _lib, _torchhost, hostcopy, ops, qerror
 from .._lib import check
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
 from . import _staging as _stg
-from ._base import _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle, _Unidirectional
+from ._base import _broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle, _Unidirectional
 from ._staging import (_DeviceStaging, _PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _int8_view, _ph,
                        _plan, _range_copies, _ranges, _rows_from_ptrs, _serialized, _stage_in, _stage_rows,
                        _staging, phase_clock)  # noqa: F401  (phase_clock: re-exported, bench.py uses it from here)
@@ -564,27 +564,6 @@ def _encode_delta_dict_packed(prevs: List[torch.Tensor], news: List[torch.Tensor
                                                  scales=st.buf("scales", lay.ntensors, torch.float32),
                                                  partials=st.buf("partials", lay.nchunks, torch.int32))
     return _packed_out(names, news, lay, st, p_dev, s_dev, host_ok, numel)
-
-
-def _broadcast_groups(params_prev: Parameters, pairs, dev: torch.device):
-    """broadcast_delta_'s fused entries as [names], one list per placement of params_new (on the staging device,
-    on the CPU). An ndim > 1 pair (hidden, new) — fp32, of one shape and non-empty: _delta_pairs saw to that — is
-    fused when the hidden tensor is the caller's own, contiguous and on the staging device, `new` is contiguous
-    there or anywhere on the CPU, and the two do not share storage. Every other pair takes send_delta's encode
-    and receive_add_'s update."""
-    on_dev: List[str] = []
-    on_cpu: List[str] = []
-    for n, (h, g) in pairs.items():
-        if (h is not params_prev[n] or not h.is_cuda or h.device != dev or not h.is_contiguous()
-                or h.dtype != torch.float32 or g.dtype != torch.float32):
-            continue
-        if g.is_cuda:
-            if (g.device == dev and g.is_contiguous()
-                    and g.untyped_storage().data_ptr() != h.untyped_storage().data_ptr()):
-                on_dev.append(n)
-        elif g.device.type == "cpu":
-            on_cpu.append(n)
-    return [g for g in (on_dev, on_cpu) if g]
 
 
 @_serialized

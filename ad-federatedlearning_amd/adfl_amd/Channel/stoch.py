@@ -50,7 +50,8 @@ from .. import stoch as sops
 from .._lib import check
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
 from . import _staging as _stg
-from ._base import _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle, _Unidirectional
+from ._base import (_broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle,
+                    _Unidirectional)
 from ._staging import (_PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _ph, _range_copies, _ranges,
                        _rows_from_ptrs, _serialized, _stage_in, _stage_rows, _staging)
 
@@ -291,6 +292,106 @@ def _encode_delta_stoch(prevs: List[torch.Tensor], news: List[torch.Tensor], nam
     datas, sgs, nm = _hand_out_planes(lv, sg, lay, news, [not t.is_cuda for t in news], st, norms_list,
                                       native_like=True)
     return _payloads(names, datas, sgs, nm, lay.ntensors, codec)
+
+
+def _on_device_or_staged(tensors: List[torch.Tensor], direct: List[bool], st, key: str) -> List[torch.Tensor]:
+    """`tensors` as contiguous fp32 tensors on the staging device: the tensor itself where direct[k], else its
+    slot of a compact bucket `key` the others are staged into together (one H2D for CPU tensors, one gather
+    launch for device ones: _stage_in)."""
+    rest = [k for k, d in enumerate(direct) if not d]
+    if not rest:
+        return list(tensors)
+    sub = st.layout(tuple(int(tensors[k].numel()) for k in rest))
+    buf = _stage_in([tensors[k] for k in rest], sub, st, key, torch.float32)
+    out = list(tensors)
+    for k, o, n in zip(rest, sub.offsets.tolist(), sub.sizes.tolist()):
+        out[k] = buf[o:o + n]
+    return out
+
+
+@_serialized
+def _encode_delta_update_stoch(hiddens: List[torch.Tensor], news: List[torch.Tensor], names: List[str],
+                               fused: List[bool], codec: str, bits: int, uniforms=None, seed=None,
+                               torch_norm: bool = True):
+    """_encode_delta_stoch(hiddens, news, ...) — the same payloads, the same single draw from torch's CPU
+    generator, each element's uniform that of its index in the compact bucket of all of `names` — which also
+    leaves hiddens[k] += decode(payload k) for every fused[k] (_broadcast_groups' entries), without the payload
+    coming back in. Returns (payloads, the names whose hidden tensor is updated).
+
+    One launch sequence covers every entry, so the draws cannot depend on which entries fuse. A fused hidden
+    tensor is read and written where it is; a `new` tensor that is contiguous on the device is read where it
+    is, any other is staged into the compact "x" bucket (params_new on the CPU: one H2D, the pointer table is
+    the bucket's slots). An entry that does not fuse has its hidden tensor staged too ("x_prev"); the kernels
+    then update that copy, which is dropped — the caller runs receive_add_ for it. Routes:
+      rqsgd  sops.rqsgd_encode_delta_update_batched (planes in the 64-element-aligned bucket, ushift keeping the
+             compact draws, as _encode_delta_stoch);
+      qsgd, reference norm: ops.bucket_diff into the compact bucket, sops.reference_norms, then
+             sops.qsgd_quantize_update_batched;
+      cnat, and qsgd under ADFL_STOCH_NORM=fp64: bucket_diff and _codec_encode as send_delta runs them, then
+             sops.dequantize_axpby_batched (alpha = beta = 1: fp32(fp32(1 * h) + fp32(1 * d)) = fp32(h + d)) over
+             the planes where the encode left them, for the fused entries whose hidden tensor is 16-byte aligned
+             (what that op takes; the others are left to receive_add_)."""
+    st = _staging()
+    dev = st.device
+    th = _torchhost.get()
+    sizes = tuple(int(t.numel()) for t in news)
+    compact = st.layout(sizes)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    two_step = codec == "cnat" or (codec == "qsgd" and not torch_norm)
+    if two_step:
+        fused = [f and h.data_ptr() % 16 == 0 for f, h in zip(fused, hiddens)]
+    n_direct = [t.is_cuda and t.device == dev and t.is_contiguous() for t in news]
+    n_list = _on_device_or_staged(news, n_direct, st, "x")
+    h_list = _on_device_or_staged(hiddens, fused, st, "x_prev")
+    ok_n, _, n_ptrs = th.device_ptrs(n_list, dev.index, 4)
+    ok_h, _, h_ptrs = th.device_ptrs(h_list, dev.index, 4)
+    if not (ok_n and ok_h):
+        raise ValueError("broadcast_delta_: the fused tensors must be contiguous fp32 tensors on the device")
+    lay, ushift = compact, None
+    if codec == "rqsgd":
+        lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
+        ushift = _ushift_for(lay, compact)
+    ws = st.buf("stoch_ws", lay.nchunks * 16, torch.uint8)
+    levels, signs = st.buf("s_levels", lay.total, torch.uint8), st.buf("s_signs", lay.total, torch.int8)
+    norms = st.buf("s_norms", lay.ntensors, torch.float32)
+    mins = st.buf("s_mins", lay.ntensors, torch.float32) if codec == "rqsgd" else None
+    done = [n for n, f in zip(names, fused) if f]
+    with torch.no_grad():
+        if codec == "rqsgd":
+            lv, sg, _, _ = sops.rqsgd_encode_delta_update_batched(
+                n_list, h_list, lay, bits, ptrs=(n_ptrs, h_ptrs), ushift=ushift, uniforms=uniforms, seed=seed,
+                counter=0, levels=levels, signs=signs, norms=norms, mins=mins, ws=ws)
+        else:
+            x_dev = ops.bucket_diff(n_list, h_list, lay, ptrs=(n_ptrs, h_ptrs),
+                                    out=st.buf("x" if all(n_direct) else "x_diff", lay.total, torch.float32))
+            if not two_step:
+                sops.reference_norms(x_dev, lay, out32=norms)
+                lv, sg = sops.qsgd_quantize_update_batched(x_dev, lay, bits, norms, h_list, ptrs=h_ptrs,
+                                                           uniforms=uniforms, seed=seed, counter=0, levels=levels,
+                                                           signs=signs)
+            else:
+                lv, sg = _codec_encode(codec, x_dev, lay, bits, uniforms, seed, levels, signs, norms, mins, ws,
+                                       torch_norm)
+                idx = [k for k, f in enumerate(fused) if f]
+                if idx:
+                    sub, nr = lay, norms
+                    if len(idx) < len(names):   # the fused entries alone, at their offsets in the planes
+                        sub = ops.layout_for(torch.from_numpy(lay.offsets[idx]), torch.from_numpy(lay.sizes[idx]))
+                        nr = norms[torch.tensor(idx, device=dev)]
+                    own = [hiddens[k] for k in idx]
+                    sops.dequantize_axpby_batched(codec, lv, sg, nr, sub, bits, [own], [own], 1.0, 1.0)
+    nm_host = st.buf("s_norms_host", 2 * lay.ntensors, torch.float32, pinned=True)
+    nm_host[:lay.ntensors].copy_(norms, non_blocking=True)
+    if mins is not None:
+        nm_host[lay.ntensors:].copy_(mins, non_blocking=True)
+
+    def norms_list():
+        torch.cuda.current_stream(dev).synchronize()
+        return nm_host.tolist()
+    datas, sgs, nm = _hand_out_planes(lv, sg, lay, news, [not t.is_cuda for t in news], st, norms_list,
+                                      native_like=True)
+    return _payloads(names, datas, sgs, nm, lay.ntensors, codec), done
 
 
 def _range_encode_args(sub, dev) -> Tuple[int, int, int, int, int, int]:
@@ -845,9 +946,24 @@ class _StochChannel(_CodecChannel):
         q_params = self._quantize_delta(params_prev, params_new, self.bits)
         return q_params, time.perf_counter() - s_time
 
+    def broadcast_delta_(self, hidden_state: Parameters,
+                         params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``_CodecChannel.broadcast_delta_`` (QAFeL's broadcast: send_delta(hidden_state, params_new), then
+        receive_add_(c_params, [hidden_state])) with the two fused for a device-resident hidden state: the fp32
+        ndim > 1 entries ``_broadcast_groups`` names (the SLQ channels' rule) have their hidden tensors updated by
+        the encode's own launches (_encode_delta_update_stoch: the payload never comes back in), whether
+        params_new is on the device or on the CPU (staged by one H2D copy). The payload, the hidden state and
+        the draws from torch's CPU generator are send_delta + receive_add_'s bit for bit; the payload tensors
+        live where params_new's do. ndim <= 1 entries, a CPU hidden state, fp16 / bf16 / fp64 pairs and every
+        other entry take send_delta's encode and receive_add_'s update."""
+        s_time = time.perf_counter()
+        q_params = self._quantize_delta(hidden_state, params_new, self.bits, update=True)
+        return q_params, time.perf_counter() - s_time
+
     def _quantize_delta(self, params_prev: Parameters, params_new: Parameters, bits: int, uniforms=None,
-                        seed=None) -> QuantParameters:
-        """_quantize_params of the difference (same test hooks: injected uniforms cover the compact fp32 bucket)."""
+                        seed=None, update: bool = False) -> QuantParameters:
+        """_quantize_params of the difference (same test hooks: injected uniforms cover the compact fp32 bucket).
+        update: broadcast_delta_ — params_prev is the hidden state, which also takes the decoded payload."""
         cls = self.__class__.__name__
 
         def codable(name, dt, shape):   # what _quantize_params raises for the difference tensor
@@ -860,9 +976,18 @@ class _StochChannel(_CodecChannel):
             raise ValueError(f"{cls}: injected uniforms ({uniforms.dtype}) cover one dtype bucket; this dict also "
                              f"holds {sorted(str(d) for d in {pairs[n][1].dtype for n in coded})}")
         tn = reference_norm()
-        encoded = (_encode_delta_stoch([pairs[n][0] for n in f32], [pairs[n][1] for n in f32], f32, self.CODEC, bits,
-                                       uniforms if uniforms is None or uniforms.dtype == torch.float32 else None,
-                                       seed, tn) if f32 else {})
+        u32 = uniforms if uniforms is None or uniforms.dtype == torch.float32 else None
+        done: List[str] = []   # broadcast_delta_'s entries whose hidden tensor the encode has already updated
+        fuse = set()
+        if update and f32:
+            fuse = {n for grp in _broadcast_groups(params_prev, {n: pairs[n] for n in f32}, _staging().device)
+                    for n in grp}
+        if fuse:
+            encoded, done = _encode_delta_update_stoch([pairs[n][0] for n in f32], [pairs[n][1] for n in f32], f32,
+                                                       [n in fuse for n in f32], self.CODEC, bits, u32, seed, tn)
+        else:
+            encoded = (_encode_delta_stoch([pairs[n][0] for n in f32], [pairs[n][1] for n in f32], f32, self.CODEC,
+                                           bits, u32, seed, tn) if f32 else {})
         diffs: Dict[str, torch.Tensor] = {}
 
         def sub(group):   # torch's own new - prev on the pair's device (params_new's, for a pair on two)
@@ -899,6 +1024,10 @@ class _StochChannel(_CodecChannel):
                 t = plain[n]
                 out[n] = qp(t, bits, 0, pass_signs, t.shape, t.dtype, t.dtype, 0)
             size += out[n].data.nbytes   # one byte per encoded element
+        if update:   # the entries the fused launches did not take: receive_add_ of their payloads
+            rest = {n: p for n, p in out.items() if n not in done}
+            if rest:
+                self.receive_add_(QuantParameters(rest, 0), [{n: params_prev[n] for n in rest}])
         return QuantParameters(out, size)
 
     def _quantize_params(self, params: Parameters, bits: int, uniforms=None, seed=None) -> QuantParameters:

@@ -108,6 +108,10 @@ SIGNATURES = {
     "adfl_cnat_encode_batched_work": (INT, [P, P, I64, P, I64, INT, P, U64, U64, P, I64, P, P, P, P]),
     "adfl_rqsgd_encode_delta_batched": (INT, [P, P, P, I64, INT, P, P, U64, U64, P, I64, P, P, P, P, P]),
     "adfl_rqsgd_encode_delta_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, U64, U64, P, I64, P, P, P, P, P]),
+    "adfl_rqsgd_encode_delta_update_batched": (INT, [P, P, P, I64, INT, P, P, U64, U64, P, I64, P, P, P, P, P]),
+    "adfl_rqsgd_encode_delta_update_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, U64, U64, P, I64, P, P, P, P,
+                                                          P]),
+    "adfl_qsgd_quantize_update_batched": (INT, [P, P, I64, INT, P, P, U64, U64, P, P, P, I64, P]),
     "adfl_bucket_diff": (INT, [P, P, I64, P, P, P]),
     "adfl_philox_uniforms": (INT, [P, I64, I64, U64, U64, P]),
     "adfl_stoch_norms_batched_dt": (INT, [I32, P, P, I64, INT, P, I64, P, P, P]),

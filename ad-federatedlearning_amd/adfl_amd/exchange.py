@@ -291,7 +291,10 @@ class PeerExchange:
             self.exchange_mean(x, out)      # communicators and streams warmed outside the capture
             with torch.cuda.graph(g, stream=cap):
                 self.exchange_mean(x, out)
-                for s in (self.quant_stream, self.gather_stream):   # every forked stream rejoins the capture
+                # every forked stream rejoins the capture. In order on the caller's stream (encode_and_gather's
+                # first branch) nothing forks: an event recorded there on a side stream would be recorded
+                # outside the capture while it is open
+                for s in ((self.quant_stream, self.gather_stream) if self.side_stream else ()):
                     cap.wait_stream(s)
         torch.cuda.current_stream(self.device).wait_stream(cap)
         return ExchangeGraph(g, x, out, self)

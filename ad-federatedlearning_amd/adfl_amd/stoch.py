@@ -7,6 +7,8 @@ Every function takes and returns CUDA (HIP) tensors over a bucketed flat buffer 
   (Src/ADFL/Channel/quant.py:223-252)
 * ``rqsgd_encode_batched`` / ``rqsgd_decode_batched`` — RQSGDChannel (quant.py:364-398)
 * ``cnat_encode_batched`` / ``cnat_decode_batched``   — CNATChannel (quant.py:509-545)
+* ``rqsgd_encode_delta_batched`` — RQSGD of ``new - prev`` from two sources; ``rqsgd_encode_delta_update_batched``
+  / ``qsgd_quantize_update_batched`` — QAFeL's broadcast: the encode that also leaves ``hidden += decode(payload)``
 * ``norms_batched`` — per-tensor ||x||_2 or (max|x|, min|x|); ``qsgd_quantize_batched`` — levels from
   given norms (what the parity tests use to inject the reference's own norm)
 
@@ -29,7 +31,9 @@ from .ops import BucketLayout, _dev, _stream
 
 __all__ = ["RngStream", "norms_batched", "qsgd_quantize_batched", "qsgd_encode_batched", "rqsgd_encode_batched",
            "qsgd_decode_batched", "rqsgd_decode_batched", "cnat_encode_batched", "cnat_decode_batched",
-           "philox_uniforms", "workspace", "rqsgd_encode_delta_batched", "torch_norms", "NORM_L2", "NORM_LINF", "NORM_L2_TORCH", "DT_DTYPES", "encode_batched_dt",
+           "philox_uniforms", "workspace", "rqsgd_encode_delta_batched",
+           "rqsgd_encode_delta_update_batched", "qsgd_quantize_update_batched",
+           "torch_norms", "NORM_L2", "NORM_LINF", "NORM_L2_TORCH", "DT_DTYPES", "encode_batched_dt",
            "quantize_batched_dt", "norms_batched_dt", "philox_uniforms_dt", "dequantize_mean_batched"]
 
 
@@ -253,6 +257,92 @@ def _ushift(ushift, layout: BucketLayout, dev):
     return cache[key], us
 
 
+def _rqsgd_delta(entry: str, n_tab, p_tab, dev, layout: BucketLayout, bits: int, ushift, uniforms, seed, counter,
+                 levels, signs, norms, mins, ws, work):
+    """The shared tail of rqsgd_encode_delta_batched / rqsgd_encode_delta_update_batched: the checks the C ABI
+    cannot make, the outputs, and the launch of `entry`."""
+    us, us_host = _ushift(ushift, layout, dev)
+    if uniforms is not None:
+        top = int((layout.offsets + layout.sizes + us_host).max())
+        if uniforms.dtype != torch.float32 or uniforms.numel() < top:
+            raise ValueError("adfl_amd.stoch: uniforms must be an fp32 plane covering the shifted layout")
+        if not uniforms.is_cuda or not uniforms.is_contiguous() or uniforms.data_ptr() % 16:
+            raise ValueError("adfl_amd.stoch: uniforms must be a contiguous, 16-byte aligned device tensor")
+    levels, signs = _planes(layout, dev, levels, signs, torch.uint8)
+    norms = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if norms is None else norms
+    mins = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if mins is None else mins
+    ws = _ws(ws, layout, dev)
+    check(getattr(_lib.load(), entry)(
+        n_tab.data_ptr(), p_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        *work, bits, uniforms.data_ptr() if uniforms is not None else None,
+        us.data_ptr() if us is not None else None, seed, counter, ws.data_ptr(), ws.numel(), levels.data_ptr(),
+        signs.data_ptr(), norms.data_ptr(), mins.data_ptr(), _stream(dev)))
+    return levels, signs, norms, mins
+
+
+# rqsgd_encode_delta_update_batched over a resident-eligible layout with resident=None: "resident" (one launch, h
+# re-read stage by stage) or "twopass". DESIGN.md §10 has the measurement that chose it.
+_UPDATE_RESIDENT_FORM = "resident"
+
+
+def rqsgd_encode_delta_update_batched(new, hidden, layout: BucketLayout, bits: int, *, ptrs=None, ushift=None,
+                                      uniforms: Optional[torch.Tensor] = None, seed: int = 0, counter: int = 0,
+                                      levels: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None,
+                                      norms: Optional[torch.Tensor] = None, mins: Optional[torch.Tensor] = None,
+                                      ws: Optional[torch.Tensor] = None, resident: Optional[bool] = None):
+    """QAFeL's broadcast (Src/ADFL/Server/qafel.py:156-180) for RQSGD: ``rqsgd_encode_delta_batched(new, hidden)``
+    and, in place, ``hidden += rqsgd_decode(payload)`` — per element fp32(h + d), d the decode kernel's value for
+    the stored level and sign bytes under the tensor's max and min (+0 for a zero norm, still added) —
+    bit-identical to the encode followed by rqsgd_decode_batched and an fp32 add
+    (adfl_rqsgd_encode_delta_update_batched_work). Sources, ushift, uniforms and outputs as
+    rqsgd_encode_delta_batched takes them; `hidden` must be writable fp32 on the device (a contiguous flat buffer
+    in `layout`, or a list of contiguous tensors of its sizes), must not overlap `new`, and is the only thing
+    modified besides the outputs. resident: None = the form measured faster where both apply
+    (_UPDATE_RESIDENT_FORM), True = the one launch whenever the layout allows it, False = the two passes; the
+    same bytes. ptrs: see ops._delta_tables."""
+    from .ops import _delta_nwork, _update_tables
+    if ptrs is None:
+        _delta_f32(new, "new")
+        _delta_f32(hidden, "hidden")
+    dev, n_tab, h_tab, _keep = _update_tables(new, hidden, layout, ptrs, "rqsgd_encode_delta_update_batched")
+    if resident is None and _UPDATE_RESIDENT_FORM != "resident":
+        resident = False
+    work = _work(layout, dev, resident) if _delta_nwork(layout) else (0, 0)
+    return _rqsgd_delta("adfl_rqsgd_encode_delta_update_batched_work", n_tab, h_tab, dev, layout, bits, ushift,
+                        uniforms, seed, counter, levels, signs, norms, mins, ws, work)
+
+
+def qsgd_quantize_update_batched(flat: torch.Tensor, layout: BucketLayout, bits: int, norms: torch.Tensor, hidden, *,
+                                 ptrs=None, uniforms: Optional[torch.Tensor] = None, seed: int = 0, counter: int = 0,
+                                 levels: Optional[torch.Tensor] = None,
+                                 signs: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """QAFeL's broadcast for QSGD under given norms: ``qsgd_quantize_batched(flat, ...)`` over the difference
+    bucket flat = new - hidden (ops.bucket_diff) and, in place, ``hidden += qsgd_decode(payload)`` — fp32(h + d)
+    per element, bit-identical to the quantize followed by qsgd_decode_batched and an fp32 add
+    (adfl_qsgd_quantize_update_batched). `hidden`: a contiguous flat fp32 device buffer in `layout` or a list of
+    contiguous fp32 device tensors of its sizes, any addresses, not overlapping `flat`; the only thing modified
+    besides the outputs. ptrs: hidden's data pointers as a CPU int64 tensor when the caller has checked the list."""
+    from .ops import _delta_sources
+    flat = _check_flat(flat, layout)
+    dev = flat.device
+    if ptrs is not None:
+        if len(hidden) != layout.ntensors:
+            raise ValueError(f"qsgd_quantize_update_batched: {len(hidden)} tensors for a layout of {layout.ntensors}")
+        h_tab = ptrs.to(dev, non_blocking=True)
+    else:
+        _delta_f32(hidden, "hidden")
+        if isinstance(hidden, torch.Tensor) and not hidden.is_contiguous():
+            raise ValueError("qsgd_quantize_update_batched: hidden must be contiguous (it is updated in place)")
+        h_tab, _keep = _delta_sources(hidden, layout, dev, "hidden")
+    levels, signs = _planes(layout, dev, levels, signs, torch.uint8)
+    check(_lib.load().adfl_qsgd_quantize_update_batched(flat.data_ptr(), layout.device_chunks(dev).data_ptr(),
+                                                        layout.nchunks, bits, _dev(norms, "norms").data_ptr(),
+                                                        _uniforms(uniforms, layout), seed, counter, levels.data_ptr(),
+                                                        signs.data_ptr(), h_tab.data_ptr(), layout.ntensors,
+                                                        _stream(dev)))
+    return levels, signs
+
+
 def rqsgd_encode_delta_batched(new, prev, layout: BucketLayout, bits: int, *, ptrs=None, ushift=None,
                                uniforms: Optional[torch.Tensor] = None, seed: int = 0, counter: int = 0,
                                levels: Optional[torch.Tensor] = None, signs: Optional[torch.Tensor] = None,
@@ -274,26 +364,11 @@ def rqsgd_encode_delta_batched(new, prev, layout: BucketLayout, bits: int, *, pt
         _delta_f32(prev, "prev")
     dev = _delta_device(new, prev)
     n_tab, p_tab, _keep = _delta_tables(new, prev, layout, dev, ptrs)
-    us, us_host = _ushift(ushift, layout, dev)
-    if uniforms is not None:
-        top = int((layout.offsets + layout.sizes + us_host).max())
-        if uniforms.dtype != torch.float32 or uniforms.numel() < top:
-            raise ValueError("adfl_amd.stoch: uniforms must be an fp32 plane covering the shifted layout")
-        if not uniforms.is_cuda or not uniforms.is_contiguous() or uniforms.data_ptr() % 16:
-            raise ValueError("adfl_amd.stoch: uniforms must be a contiguous, 16-byte aligned device tensor")
-    levels, signs = _planes(layout, dev, levels, signs, torch.uint8)
-    norms = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if norms is None else norms
-    mins = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if mins is None else mins
-    ws = _ws(ws, layout, dev)
     # the work list is the resident encodes' (ADFL_SLQ_RESIDENT_CHUNKS); the delta kernel takes tensors up to
     # ADFL_SLQ_DELTA_RESIDENT_CHUNKS, so a layout beyond that bound runs the two passes (ops._delta_nwork's guard)
     work = _work(layout, dev, resident) if _delta_nwork(layout) else (0, 0)
-    check(_lib.load().adfl_rqsgd_encode_delta_batched_work(
-        n_tab.data_ptr(), p_tab.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
-        *work, bits, uniforms.data_ptr() if uniforms is not None else None,
-        us.data_ptr() if us is not None else None, seed, counter, ws.data_ptr(), ws.numel(), levels.data_ptr(),
-        signs.data_ptr(), norms.data_ptr(), mins.data_ptr(), _stream(dev)))
-    return levels, signs, norms, mins
+    return _rqsgd_delta("adfl_rqsgd_encode_delta_batched_work", n_tab, p_tab, dev, layout, bits, ushift, uniforms,
+                        seed, counter, levels, signs, norms, mins, ws, work)
 
 
 def qsgd_decode_batched(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor, layout: BucketLayout,
@@ -567,6 +642,53 @@ def stoch_encode_delta_batched_op(new: torch.Tensor, prev: torch.Tensor, offsets
 
 @stoch_encode_delta_batched_op.register_fake
 def _(new, prev, offsets, sizes, codec, bits, seed, counter):
+    n, t = new.numel(), sizes.numel()
+    return (new.new_empty((n,), dtype=torch.int8 if codec == "cnat" else torch.uint8),
+            new.new_empty((n,), dtype=torch.int8), new.new_empty((t,), dtype=torch.float32),
+            new.new_empty((t,), dtype=torch.float32))
+
+
+# QAFeL's broadcast (torch.ops.adfl_apply.*, beside the other server steps).
+@torch.library.custom_op("adfl_apply::stoch_encode_delta_update_batched", mutates_args=("hidden",))
+def stoch_encode_delta_update_batched_op(new: torch.Tensor, hidden: torch.Tensor, offsets: torch.Tensor,
+                                         sizes: torch.Tensor, codec: str, bits: int, seed: int,
+                                         counter: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """stoch_encode_delta_batched(new, hidden), and in place hidden += decode(payload): fp32(h + d) per element of
+    every tensor of the caller-placed layout, d the codec's decode of the stored bytes (+0 for a zero norm);
+    positions no tensor owns are untouched. rqsgd: the two-source kernels that also write h'; qsgd under the
+    reference norm (the default): bucket_diff, the reference-order norm, then the quantize that also writes h';
+    cnat, and qsgd under ADFL_STOCH_NORM=fp64: stoch_encode_delta_batched's encode, then the fused decode + axpby
+    (alpha = beta = 1) over the planes where the encode left them."""
+    from .Channel.stoch import reference_norm
+    from .ops import _filled, _update_flat, bucket_diff, layout_for
+    _check_codec(codec)
+    if new.dtype != torch.float32:
+        raise ValueError(f"stoch_encode_delta_update_batched: fp32 buffers only, got {new.dtype} / {hidden.dtype}")
+    lay = layout_for(offsets, sizes)
+    new, hidden = _update_flat(new, hidden, lay, "stoch_encode_delta_update_batched")
+    dev = new.device
+    n = new.numel()
+    lv = _filled(n, torch.int8 if codec == "cnat" else torch.uint8, dev, lay)
+    sg = _filled(n, torch.int8, dev, lay)
+    mins = torch.zeros(lay.ntensors, dtype=torch.float32, device=dev)
+    if codec == "rqsgd":
+        return rqsgd_encode_delta_update_batched(new, hidden, lay, bits, seed=seed, counter=counter, levels=lv,
+                                                 signs=sg, mins=mins)
+    diff = bucket_diff(new, hidden, lay, out=torch.empty(n, dtype=torch.float32, device=dev))
+    if codec == "qsgd" and reference_norm():
+        norms = torch_norms(diff, lay)
+        qsgd_quantize_update_batched(diff, lay, bits, norms, hidden, seed=seed, counter=counter, levels=lv, signs=sg)
+        return lv, sg, norms, mins
+    if codec == "qsgd":
+        lv, sg, norms = qsgd_encode_batched(diff, lay, bits, seed=seed, counter=counter, levels=lv, signs=sg)
+    else:
+        lv, sg, norms = cnat_encode_batched(diff, lay, bits, seed=seed, counter=counter, exps=lv, signs=sg)
+    dequantize_axpby_batched(codec, lv, sg, norms, lay, bits, hidden, hidden, 1.0, 1.0)
+    return lv, sg, norms, mins
+
+
+@stoch_encode_delta_update_batched_op.register_fake
+def _(new, hidden, offsets, sizes, codec, bits, seed, counter):
     n, t = new.numel(), sizes.numel()
     return (new.new_empty((n,), dtype=torch.int8 if codec == "cnat" else torch.uint8),
             new.new_empty((n,), dtype=torch.int8), new.new_empty((t,), dtype=torch.float32),

@@ -40,11 +40,7 @@
 
 namespace {
 
-// (the uniforms, the QSGD / RQSGD level rules and the register quantize body are stoch_device.h's)
-__device__ __forceinline__ float pow2i(int k) {  // 2^k for k in [-126, 128] (128 -> inf), exact
-  return __uint_as_float((uint32_t)(k + 127) << 23);
-}
-
+// (the uniforms, the QSGD / RQSGD level rules, the decoders and the register quantize body are stoch_device.h's)
 // CNAT exponent byte (quant.py:516-532). v = fl(|x| + eps) >= 2^-23 is normal, so its binary exponent e and
 // the band table give floor / ceil of fl32(log2 v) exactly. Integer clamp and low byte = torch's float
 // clamp_ then .to(int8) of an integral value.
@@ -88,36 +84,6 @@ __device__ __forceinline__ uint32_t cnat_exp_fast(float x, float u, int min_e, i
   int r = e + (u < prob ? 0 : 1);
   r = min(max(r, min_e), max_e);
   return (uint32_t)(x == 0.0f ? min_e : r) & 0xffu;
-}
-
-// decoders (d divides by levels)
-__device__ __forceinline__ float qsgd_value_exact(uint32_t l, uint32_t sgn, float norm, float s) {
-  return __fdiv_rn(norm * (float)l, s) * (float)(int8_t)sgn;
-}
-
-__device__ __forceinline__ float qsgd_value_fast(uint32_t l, uint32_t sgn, float norm, const Div& d, bool& bad) {
-  return div_fast(norm * (float)l, d, bad) * (float)(int8_t)sgn;
-}
-
-__device__ __forceinline__ float rqsgd_value_exact(uint32_t l, uint32_t sgn, float norm, float mn, float s) {
-  const float sf = (float)(int8_t)sgn;
-  return l == 0u ? mn * sf : __fdiv_rn((norm * sf) * (float)l, s);
-}
-
-__device__ __forceinline__ float rqsgd_value_fast(uint32_t l, uint32_t sgn, float norm, float mn, const Div& d,
-                                                  bool& bad) {
-  const float sf = (float)(int8_t)sgn;
-  bool b2 = false;
-  const float v = div_fast((norm * sf) * (float)l, d, b2);
-  bad |= b2 & (l != 0u);
-  return l == 0u ? mn * sf : v;
-}
-
-__device__ __forceinline__ float cnat_value(uint32_t e, uint32_t sgn, float norm) {
-  const int k = (int)(int8_t)e;  // in [-128, 127]
-  // 2^k exactly: normal for k >= -126, the denormals 2^-127 / 2^-128 below
-  const float p = k >= -126 ? pow2i(k) : __uint_as_float(0x00400000u >> (-127 - k));
-  return (norm * (float)(int8_t)sgn) * p;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -376,17 +342,30 @@ __device__ __forceinline__ void quantize_chunk_vec(const float4* __restrict__ x4
 }
 
 // PB: Philox blocks generated per batch (philox4x32_batch); the product's choice is kPbQuantize.
-template <int PB>
-__global__ __launch_bounds__(kBlock) void k_qsgd_quantize(const float* __restrict__ x,
-                                                          const adfl_slq_chunk* __restrict__ chunks, float s,
-                                                          const float* __restrict__ norms, Uniforms U,
-                                                          uint8_t* __restrict__ levels, int8_t* __restrict__ signs) {
+//
+// UPD (k_qsgd_quantize_update — QAFeL's broadcast, Src/ADFL/Server/qafel.py:156-180, for QSGD under the reference
+// norm): x is the difference bucket g - h, and the pass also leaves h' = fp32(h + d) in the hidden tensors
+// themselves, d being k_stoch_dequantize<0>'s decode (decode4 / decode_exact) of the bytes this thread has just
+// stored; a zero norm decodes to +0, which is still added. h is addressed as the delta entries address a source,
+// hidden[c.tensor] + (c.start - the tensor's first element); in the compact bucket a tensor's slot and its hidden
+// tensor need not share a phase mod 16 bytes, so h's groups take 16-byte accesses where h + head is 16-byte aligned
+// (block-uniform) and 4-byte ones otherwise. A group of h is read where it is updated, by the thread that writes it
+// (held from x's loads it costs 114 VGPRs and occupancy 4 against 80 and 6).
+template <int PB, bool UPD>
+__device__ __forceinline__ void qsgd_quantize_chunk(const float* __restrict__ x,
+                                                    const adfl_slq_chunk* __restrict__ chunks, float s,
+                                                    const float* __restrict__ norms, const Uniforms& U,
+                                                    uint8_t* __restrict__ levels, int8_t* __restrict__ signs,
+                                                    float* const* __restrict__ hidden) {
   const adfl_slq_chunk c = chunks[gridDim.x - 1 - blockIdx.x];  // reverse: start on the cached tail of x
   const float norm = norms[c.tensor];
   uint8_t* lv = levels + c.start;
   int8_t* sg = signs + c.start;
+  float* hc = UPD ? hidden[c.tensor] + (c.start - chunks[c.first_chunk].start) : nullptr;
   if (norm == 0.0f) {  // quant.py:227-228
     fill_zero_norm(lv, sg, c.len);
+    if (UPD)
+      for (int i = threadIdx.x; i < c.len; i += kBlock) hc[i] = hc[i] + 0.0f;
     return;
   }
   const Div d = make_div(norm);
@@ -395,14 +374,53 @@ __global__ __launch_bounds__(kBlock) void k_qsgd_quantize(const float* __restric
   const int n4 = (c.len - head) >> 2;
   const auto fast = [&](float xv, float uv, bool& bad) { return qsgd_level_fast(xv, s, d, uv, bad); };
   const auto exact = [&](float xv, float uv) { return qsgd_level_exact(xv, s, norm, uv); };
+  const int i = edge_elem(head, head + (n4 << 2), c.len);
+  if (UPD) {
+    const Div ds = make_div(s);  // the decode divides by the level count
+    const bool vec = (reinterpret_cast<uintptr_t>(hc + head) & 15u) == 0;  // block-uniform
+    float4 v[kPer];
+    load_chunk_regs(reinterpret_cast<const float4*>(xc + head), n4, threadIdx.x, v);
+    const float eh = i >= 0 ? hc[i] : 0.0f;
+    const auto update = [&](int j, int k, bool live, uint32_t q) {  // every lane: decode4 holds a ballot
+      const float4 dv = decode4<0>(q, sign4(v[j]), norm, 0.0f, ds, s, live);
+      if (live) store_sum_h4(hc + head + 4 * k, vec, load_h4(hc + head + 4 * k, vec), dv);
+    };
+    quantize_regs<PB>(v, threadIdx.x, n4, c.start + head, U, reinterpret_cast<uint32_t*>(lv + head),
+                      reinterpret_cast<uint32_t*>(sg + head), fast, exact, !d.fast, (NormAcc<ADFL_NORM_L2>*)nullptr,
+                      nullptr, 0, update);
+    if (i >= 0) {
+      const uint32_t l = exact(xc[i], U.one(c.start + i)), g = sign_byte(xc[i]);
+      lv[i] = (uint8_t)l;
+      sg[i] = (int8_t)g;
+      hc[i] = eh + decode_exact<0>(l, g, norm, 0.0f, s);
+    }
+    return;
+  }
   quantize_chunk_vec<PB>(reinterpret_cast<const float4*>(xc + head), n4, c.start + head, U,
                          reinterpret_cast<uint32_t*>(lv + head), reinterpret_cast<uint32_t*>(sg + head), fast, exact,
                          !d.fast, (NormAcc<ADFL_NORM_L2>*)nullptr);
-  const int i = edge_elem(head, head + (n4 << 2), c.len);
   if (i >= 0) {
     lv[i] = (uint8_t)exact(xc[i], U.one(c.start + i));
     sg[i] = (int8_t)sign_byte(xc[i]);
   }
+}
+
+template <int PB>
+__global__ __launch_bounds__(kBlock) void k_qsgd_quantize(const float* __restrict__ x,
+                                                          const adfl_slq_chunk* __restrict__ chunks, float s,
+                                                          const float* __restrict__ norms, Uniforms U,
+                                                          uint8_t* __restrict__ levels, int8_t* __restrict__ signs) {
+  qsgd_quantize_chunk<PB, false>(x, chunks, s, norms, U, levels, signs, nullptr);
+}
+
+template <int PB>
+__global__ __launch_bounds__(kBlock) void k_qsgd_quantize_update(const float* __restrict__ x,
+                                                                 const adfl_slq_chunk* __restrict__ chunks, float s,
+                                                                 const float* __restrict__ norms, Uniforms U,
+                                                                 uint8_t* __restrict__ levels,
+                                                                 int8_t* __restrict__ signs,
+                                                                 float* const* __restrict__ hidden) {
+  qsgd_quantize_chunk<PB, true>(x, chunks, s, norms, U, levels, signs, hidden);
 }
 
 // CNAT: exponents + signs + the chunk's L2 partial in one read of x.
@@ -712,47 +730,6 @@ __global__ __launch_bounds__(kResBlock) void k_cnat_encode_resident(
     const adfl_slq_chunk c = chunks[ci + kc];
     fill_zero_norm(reinterpret_cast<uint8_t*>(exps) + c.start, signs + c.start, c.len, tg);
   }
-}
-
-__device__ __forceinline__ void store4_nt(float4* p, float4 d) {
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  const f4v v = {d.x, d.y, d.z, d.w};
-  __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(p));
-}
-
-// Decoders. KIND 0 = QSGD, 1 = RQSGD, 2 = CNAT.
-template <int KIND>
-__device__ __forceinline__ float decode_exact(uint32_t l, uint32_t sgn, float norm, float mn, float s) {
-  if (KIND == 0) return qsgd_value_exact(l, sgn, norm, s);
-  if (KIND == 1) return rqsgd_value_exact(l, sgn, norm, mn, s);
-  return cnat_value(l, sgn, norm);
-}
-
-template <int KIND>
-__device__ __forceinline__ float decode_fast(uint32_t l, uint32_t sgn, float norm, float mn, const Div& d, bool& bad) {
-  if (KIND == 0) return qsgd_value_fast(l, sgn, norm, d, bad);
-  if (KIND == 1) return rqsgd_value_fast(l, sgn, norm, mn, d, bad);
-  return cnat_value(l, sgn, norm);
-}
-
-// Four decoded values from one dword of levels and one of signs. The fast division path falls back to the
-// exact one for the whole wave if any live lane's quotient is in doubt (every lane must call this).
-template <int KIND>
-__device__ __forceinline__ float4 decode4(uint32_t l, uint32_t g, float norm, float mn, const Div& d, float s,
-                                          bool live) {
-  bool bad = KIND != 2 && !d.fast;
-  float4 r;
-  r.x = decode_fast<KIND>(l & 0xffu, g & 0xffu, norm, mn, d, bad);
-  r.y = decode_fast<KIND>((l >> 8) & 0xffu, (g >> 8) & 0xffu, norm, mn, d, bad);
-  r.z = decode_fast<KIND>((l >> 16) & 0xffu, (g >> 16) & 0xffu, norm, mn, d, bad);
-  r.w = decode_fast<KIND>(l >> 24, g >> 24, norm, mn, d, bad);
-  if (KIND != 2 && wave_any(bad && live)) {
-    r.x = decode_exact<KIND>(l & 0xffu, g & 0xffu, norm, mn, s);
-    r.y = decode_exact<KIND>((l >> 8) & 0xffu, (g >> 8) & 0xffu, norm, mn, s);
-    r.z = decode_exact<KIND>((l >> 16) & 0xffu, (g >> 16) & 0xffu, norm, mn, s);
-    r.w = decode_exact<KIND>(l >> 24, g >> 24, norm, mn, s);
-  }
-  return r;
 }
 
 // Decode in wave tiles of 1024 elements, the SLQ decode's shape (slq_codec.hip dequantize_tile): lane l
@@ -1084,6 +1061,22 @@ int adfl_qsgd_quantize_batched(const float* d_x, const adfl_slq_chunk* d_chunks,
   const Uniforms U{d_uniforms, seed, counter};
   hipLaunchKernelGGL(k_qsgd_quantize<kPbQuantize>, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_x, d_chunks,
                      levels_f(bits), d_norms, U, d_levels, d_signs);
+  return launch_status();
+}
+
+// adfl_qsgd_quantize_batched, and in place d_hidden[t] += decode(the stored bytes): h' = fp32(h + d).
+int adfl_qsgd_quantize_update_batched(const float* d_x, const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                      const float* d_norms, const float* d_uniforms, uint64_t seed, uint64_t counter,
+                                      uint8_t* d_levels, int8_t* d_signs, float* const* d_hidden, int64_t ntensors,
+                                      void* stream) {
+  if (!d_x || !d_norms || !d_levels || !d_signs || !d_hidden || ntensors < 1 || bad_table(d_chunks, nchunks))
+    return ADFL_E_ARG;
+  if (int s = check_bits(bits)) return s;
+  if (!aligned16(d_x) || !aligned16(d_levels) || !aligned16(d_signs) || (d_uniforms && !aligned16(d_uniforms)))
+    return ADFL_E_ALIGN;
+  const Uniforms U{d_uniforms, seed, counter};
+  hipLaunchKernelGGL(k_qsgd_quantize_update<kPbQuantize>, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream,
+                     d_x, d_chunks, levels_f(bits), d_norms, U, d_levels, d_signs, d_hidden);
   return launch_status();
 }
 

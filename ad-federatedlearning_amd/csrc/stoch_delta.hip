@@ -2,7 +2,8 @@
 // codecs: RQSGD encode of new - prev without ever writing the difference (include/adfl_stoch.h,
 // adfl_rqsgd_encode_delta_batched*). QSGD / CNAT take their scale from the torch-order L2 norm, which reads one
 // flat bucket: for them the difference is written once (adfl_bucket_diff, bucket_copy.hip) and the existing
-// encode runs over it.
+// encode runs over it. The same RQSGD kernels with UPD also leave h' = fp32(h + decode(stored bytes)) in `prev`,
+// QAFeL's hidden state (adfl_rqsgd_encode_delta_update_batched*; Src/ADFL/Server/qafel.py:156-180).
 //
 // Reference behaviour restated here (bit-exact given the same uniforms):
 //   diff    Src/ADFL/model.py:350-358            diff_parameters: params_b[k] - params_a[k] per tensor
@@ -150,10 +151,10 @@ struct NoAcc {
 #endif
 constexpr bool kStraddleNeighbour = ADFL_STRADDLE_NEIGHBOUR != 0;
 
-template <class F, class E>
-__device__ __forceinline__ void straddle_group(const float4& vj, const uint4& a, const uint4& b, int p, int k, bool live,
-                                               uint32_t* __restrict__ l4, uint32_t* __restrict__ s4, F fast, E exact,
-                                               bool all_exact) {
+template <class F, class E, class P>
+__device__ __forceinline__ void straddle_group(const float4& vj, const uint4& a, const uint4& b, int p, int j, int k,
+                                               bool live, uint32_t* __restrict__ l4, uint32_t* __restrict__ s4, F fast,
+                                               E exact, bool all_exact, P post) {
   const float4 uj = make_float4(u24(p == 1 ? a.y : p == 2 ? a.z : a.w), u24(p == 1 ? a.z : p == 2 ? a.w : b.x),
                                 u24(p == 1 ? a.w : p == 2 ? b.x : b.y), u24(p == 1 ? b.x : p == 2 ? b.y : b.z));
   bool bad = all_exact;
@@ -164,12 +165,14 @@ __device__ __forceinline__ void straddle_group(const float4& vj, const uint4& a,
     l4[k] = q;
     s4[k] = pack4(sign_byte(vj.x), sign_byte(vj.y), sign_byte(vj.z), sign_byte(vj.w));
   }
+  post(j, k, live, q);  // every lane (quantize_regs' hook)
 }
 
-template <int PB, class F, class E>
+template <int PB, class F, class E, class P = NoPost>
 __device__ __forceinline__ void quantize_regs_straddle(const float4 (&v)[kPer], int tg, int n4, int64_t u0,
                                                        const Uniforms& U, uint32_t* __restrict__ l4,
-                                                       uint32_t* __restrict__ s4, F fast, E exact, bool all_exact) {
+                                                       uint32_t* __restrict__ s4, F fast, E exact, bool all_exact,
+                                                       P post = P{}) {
   static_assert(kPer % PB == 0, "batches tile a chunk's groups");
   const int p = (int)(u0 & 3);  // block-uniform
   if (kStraddleNeighbour) {
@@ -201,7 +204,7 @@ __device__ __forceinline__ void quantize_regs_straddle(const float4 (&v)[kPer], 
         const uint32_t nx = __shfl_down(w[i].x, 1, 64), ny = __shfl_down(w[i].y, 1, 64), nz = __shfl_down(w[i].z, 1, 64);
         const uint32_t ex = __shfl(extra.x, j, 64), ey = __shfl(extra.y, j, 64), ez = __shfl(extra.z, j, 64);
         const uint4 b = make_uint4(last ? ex : nx, last ? ey : ny, last ? ez : nz, 0u);  // word 3 is never drawn (p <= 3)
-        straddle_group(v[j], w[i], b, p, k, k < n4, l4, s4, fast, exact, all_exact);
+        straddle_group(v[j], w[i], b, p, j, k, k < n4, l4, s4, fast, exact, all_exact, post);
       }
     }
     return;
@@ -222,7 +225,7 @@ __device__ __forceinline__ void quantize_regs_straddle(const float4 (&v)[kPer], 
       const int j = jb + i;
       if (j * kBlock >= n4) break;  // group-uniform
       const int k = tg + j * kBlock;
-      straddle_group(v[j], w[2 * i], w[2 * i + 1], p, k, k < n4, l4, s4, fast, exact, all_exact);
+      straddle_group(v[j], w[2 * i], w[2 * i + 1], p, j, k, k < n4, l4, s4, fast, exact, all_exact, post);
     }
   }
 }
@@ -232,9 +235,20 @@ constexpr int kPbDeltaStraddle = 2;  // groups per batch on the straddling path 
 
 // Pass 2: the two sources again, levels and signs from the finalized max / min. norm == 0 (every difference
 // +-0) gives the reference's zero branch, levels 0 and signs 1 (quant.py:368-369).
+//
+// UPD (QAFeL's broadcast, Src/ADFL/Server/qafel.py:156-180): `prev` is the server's hidden state h, and the pass
+// also leaves h' = fp32(h + d) in place, d being k_stoch_dequantize<1>'s decode (decode4 / decode_exact) of the
+// level and sign bytes this thread has just stored, under the finalized max and min: what on_client_receive then
+// add_parameters_inpace(h, d, 1, 1) leave. A zero norm decodes to +0, which is still added (-0 becomes +0).
+// Holding h's groups from the difference's loads to the store costs 31 VGPRs and an occupancy step (124 VGPRs, 4
+// waves per SIMD against 5), so a group of h is re-read where it is updated, by the thread that read it for the
+// difference, and an edge element is read before the quantize: every element of h is read for the last time before
+// the same thread writes it.
+template <bool UPD>
 __global__ __launch_bounds__(kBlock) void k_rqsgd_quantize_delta(PtrTable nws, PtrTable pvs,
                                                                  const adfl_slq_chunk* __restrict__ chunks, float s,
                                                                  const float* __restrict__ norms,
+                                                                 const float* __restrict__ mins,
                                                                  const int64_t* __restrict__ ushift, Uniforms U,
                                                                  uint8_t* __restrict__ levels,
                                                                  int8_t* __restrict__ signs) {
@@ -242,23 +256,31 @@ __global__ __launch_bounds__(kBlock) void k_rqsgd_quantize_delta(PtrTable nws, P
   const float norm = norms[c.tensor];
   uint8_t* lv = levels + c.start;
   int8_t* sg = signs + c.start;
+  const DeltaSrc src = delta_src(nws, pvs, chunks, c);
+  float* hw = const_cast<float*>(src.pv);  // UPD: the hidden tensor's chunk, written in place
+  const int tid = (int)threadIdx.x;
   if (norm == 0.0f) {
     fill_zero_norm(lv, sg, c.len);
+    if (UPD)
+      for (int i = tid; i < c.len; i += kBlock) hw[i] = hw[i] + 0.0f;
     return;
   }
-  const DeltaSrc src = delta_src(nws, pvs, chunks, c);
+  const float mn = UPD ? mins[c.tensor] : 0.0f;
   const int64_t ug = c.start + (ushift ? ushift[c.tensor] : 0);  // the chunk's first uniform index (>= 0)
   const Div d = make_div(norm);
+  const Div ds = make_div(s);  // the decode divides by the level count
   const auto fast = [&](float xv, float uv, bool& bad) { return qsgd_level_fast(xv, s, d, uv, bad); };
   const auto exact = [&](float xv, float uv) { return qsgd_level_exact(xv, s, norm, uv); };
   const int head = chunk_head4(c.start, c.len);
   const int phase = (int)((ug + head) & 3);
-  const int tid = (int)threadIdx.x;
   if (!(dev_aligned16(src.nw + head) && dev_aligned16(src.pv + head)) || (U.inj && phase)) {  // block-uniform
     for (int i = tid; i < c.len; i += kBlock) {
-      const float x = delta1(src.nw, src.pv, i);
-      lv[i] = (uint8_t)exact(x, U.one(ug + i));
-      sg[i] = (int8_t)sign_byte(x);
+      const float h = ld_nt(src.pv + i);
+      const float x = ld_nt(src.nw + i) - h;
+      const uint32_t l = exact(x, U.one(ug + i)), g = sign_byte(x);
+      lv[i] = (uint8_t)l;
+      sg[i] = (int8_t)g;
+      if (UPD) hw[i] = h + decode_exact<1>(l, g, norm, mn, s);
     }
     return;
   }
@@ -266,16 +288,31 @@ __global__ __launch_bounds__(kBlock) void k_rqsgd_quantize_delta(PtrTable nws, P
   float4 v[kPer];
   load_delta_regs(reinterpret_cast<const float4*>(src.nw + head), reinterpret_cast<const float4*>(src.pv + head), n4, v);
   const int i = edge_elem(head, head + (n4 << 2), c.len);
-  const float ev = i >= 0 ? delta1(src.nw, src.pv, i) : 0.0f;
+  const float eh = i >= 0 ? ld_nt(src.pv + i) : 0.0f;
+  const float ev = i >= 0 ? ld_nt(src.nw + i) - eh : 0.0f;
   uint32_t* l4 = reinterpret_cast<uint32_t*>(lv + head);
   uint32_t* s4 = reinterpret_cast<uint32_t*>(sg + head);
-  if (phase == 0)
-    quantize_regs<kPbDelta>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr);
-  else
-    quantize_regs_straddle<kPbDeltaStraddle>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast);
+  const auto update = [&](int j, int k, bool live, uint32_t q) {  // every lane: decode4 holds a ballot
+    const float4 dv = decode4<1>(q, sign4(v[j]), norm, mn, ds, s, live);
+    if (live) store_sum_h4(hw + head + 4 * k, true, load_h4(hw + head + 4 * k, true), dv);
+  };
+  if (UPD) {
+    if (phase == 0)
+      quantize_regs<kPbDelta>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr, nullptr, 0,
+                              update);
+    else
+      quantize_regs_straddle<kPbDeltaStraddle>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast, update);
+  } else {
+    if (phase == 0)
+      quantize_regs<kPbDelta>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr);
+    else
+      quantize_regs_straddle<kPbDeltaStraddle>(v, tid, n4, ug + head, U, l4, s4, fast, exact, !d.fast);
+  }
   if (i >= 0) {
-    lv[i] = (uint8_t)exact(ev, U.one(ug + i));
-    sg[i] = (int8_t)sign_byte(ev);
+    const uint32_t l = exact(ev, U.one(ug + i)), g = sign_byte(ev);
+    lv[i] = (uint8_t)l;
+    sg[i] = (int8_t)g;
+    if (UPD) hw[i] = eh + decode_exact<1>(l, g, norm, mn, s);
   }
 }
 
@@ -316,6 +353,12 @@ __device__ __forceinline__ uint2 block_maxmin_res(uint32_t mx, uint32_t mn, uint
   return make_uint2(mx, mn);
 }
 
+//
+// UPD: k_rqsgd_quantize_delta<true>'s update in the one launch. The difference fills the registers (124 VGPRs), so
+// a stage re-reads its groups of h after quantizing them and stores h' = fp32(h + d): the thread that writes a
+// group is the one that read it for the difference, after the block's reduction (every read for the max / min
+// precedes every write), and an edge element's h is re-read by the thread that holds its difference.
+template <bool UPD>
 __global__ __launch_bounds__(kResBlock) void k_rqsgd_encode_delta_resident(
     PtrTable nws, PtrTable pvs, const adfl_slq_chunk* __restrict__ chunks, const int32_t* __restrict__ work, float lev,
     const int64_t* __restrict__ ushift, Uniforms U, uint8_t* __restrict__ levels, int8_t* __restrict__ signs,
@@ -331,6 +374,7 @@ __global__ __launch_bounds__(kResBlock) void k_rqsgd_encode_delta_resident(
   const int tg = threadIdx.x % kBlock;
   const float* nw = nws[ct.tensor];  // ci is the tensor's first chunk
   const float* pv = pvs[ct.tensor];
+  float* hw = const_cast<float*>(pv);  // UPD: the hidden tensor, written in place
   const int64_t ut = ct.start + (ushift ? ushift[ct.tensor] : 0);  // the tensor's first uniform index (>= 0)
   const int head0 = (int)((4 - (ct.start & 3)) & 3);                // every chunk's head (its len permitting)
   const int phase = (int)((ut + head0) & 3);
@@ -345,20 +389,25 @@ __global__ __launch_bounds__(kResBlock) void k_rqsgd_encode_delta_resident(
     const uint2 r = block_maxmin_res(mx, mi, red_mx, red_mn);
     const bool nan = r.x > 0x7f800000u;
     const float norm = nan ? __builtin_nanf("") : __uint_as_float(r.x);
+    const float mn = nan ? __builtin_nanf("") : __uint_as_float(r.y);
     if (threadIdx.x == 0) {
       norms[ct.tensor] = norm;
-      mins[ct.tensor] = nan ? __builtin_nanf("") : __uint_as_float(r.y);
+      mins[ct.tensor] = mn;
     }
     uint8_t* lv = levels + ct.start;
     int8_t* sg = signs + ct.start;
-    for (int i = threadIdx.x; i < len; i += kResBlock) {
+    for (int i = threadIdx.x; i < len; i += kResBlock) {  // the indices this thread read above
       if (norm == 0.0f) {
         lv[i] = 0;
         sg[i] = 1;
+        if (UPD) hw[i] = hw[i] + 0.0f;
       } else {
-        const float x = nw[i] - pv[i];
-        lv[i] = (uint8_t)qsgd_level_exact(x, lev, norm, U.one(ut + i));
-        sg[i] = (int8_t)sign_byte(x);
+        const float h = pv[i];
+        const float x = nw[i] - h;
+        const uint32_t l = qsgd_level_exact(x, lev, norm, U.one(ut + i)), g = sign_byte(x);
+        lv[i] = (uint8_t)l;
+        sg[i] = (int8_t)g;
+        if (UPD) hw[i] = h + decode_exact<1>(l, g, norm, mn, lev);
       }
     }
     return;
@@ -401,11 +450,13 @@ __global__ __launch_bounds__(kResBlock) void k_rqsgd_encode_delta_resident(
   const uint2 red = block_maxmin_res(mx, mi, red_mx, red_mn);
   const bool nan = red.x > 0x7f800000u;
   const float norm = nan ? __builtin_nanf("") : __uint_as_float(red.x);
+  const float mn = nan ? __builtin_nanf("") : __uint_as_float(red.y);
   if (threadIdx.x == 0) {
     norms[ct.tensor] = norm;
-    mins[ct.tensor] = nan ? __builtin_nanf("") : __uint_as_float(red.y);
+    mins[ct.tensor] = mn;
   }
   const Div d = make_div(norm);
+  const Div ds = make_div(lev);  // the decode divides by the level count
   const auto fast = [&](float xv, float uv, bool& bad) { return qsgd_level_fast(xv, lev, d, uv, bad); };
   const auto exact = [&](float xv, float uv) { return qsgd_level_exact(xv, lev, norm, uv); };
   // Stage r's quantize with r a compile-time constant: as a loop over r the compiler declined to unroll this body
@@ -417,21 +468,39 @@ __global__ __launch_bounds__(kResBlock) void k_rqsgd_encode_delta_resident(
     const adfl_slq_chunk c = chunks[ci + kc];
     uint8_t* lv = levels + c.start;
     int8_t* sg = signs + c.start;
+    float* hc = hw + (c.start - ct.start);
     if (norm == 0.0f) {
       fill_zero_norm(lv, sg, c.len, tg);
+      if (UPD)
+        for (int i = tg; i < c.len; i += kBlock) hc[i] = hc[i] + 0.0f;
       return;
     }
     const int head = chunk_head4(c.start, c.len);
     const int64_t ug = ut + (c.start - ct.start);
     uint32_t* l4 = reinterpret_cast<uint32_t*>(lv + head);
     uint32_t* s4 = reinterpret_cast<uint32_t*>(sg + head);
-    if (phase == 0)
-      quantize_regs<kPbDeltaResident>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr);
-    else
-      quantize_regs_straddle<kPbDeltaResident / 2>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast);
+    const auto update = [&](int j, int k, bool live, uint32_t q) {  // every lane: decode4 holds a ballot
+      const float4 dv = decode4<1>(q, sign4(v[r][j]), norm, mn, ds, lev, live);
+      if (live) store_sum_h4(hc + head + 4 * k, true, load_h4(hc + head + 4 * k, true), dv);
+    };
+    if (UPD) {
+      if (phase == 0)
+        quantize_regs<kPbDeltaResident>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr,
+                                        nullptr, 0, update);
+      else
+        quantize_regs_straddle<kPbDeltaResident / 2>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast,
+                                                     update);
+    } else {
+      if (phase == 0)
+        quantize_regs<kPbDeltaResident>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast, (NoAcc*)nullptr);
+      else
+        quantize_regs_straddle<kPbDeltaResident / 2>(v[r], tg, n4s[r], ug + head, U, l4, s4, fast, exact, !d.fast);
+    }
     if (ei[r] >= 0) {
-      lv[ei[r]] = (uint8_t)exact(ev[r], U.one(ug + ei[r]));
-      sg[ei[r]] = (int8_t)sign_byte(ev[r]);
+      const uint32_t l = exact(ev[r], U.one(ug + ei[r])), g = sign_byte(ev[r]);
+      lv[ei[r]] = (uint8_t)l;
+      sg[ei[r]] = (int8_t)g;
+      if (UPD) hc[ei[r]] = hc[ei[r]] + decode_exact<1>(l, g, norm, mn, lev);
     }
   };
   static_assert(kResPerGroup == 2, "two stages");
@@ -467,15 +536,12 @@ inline int check_delta_args(const void* d_new, const void* d_prev, const void* d
   return ADFL_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int adfl_rqsgd_encode_delta_batched(const float* const* d_new, const float* const* d_prev,
-                                    const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
-                                    const float* d_uniforms, const int64_t* d_ushift, uint64_t seed, uint64_t counter,
-                                    void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels, int8_t* d_signs,
-                                    float* d_norms, float* d_mins, void* stream) {
+// The two passes and the one launch, without (UPD false: d_prev is read only) or with the hidden-state update.
+template <bool UPD>
+int rqsgd_delta_twopass(const float* const* d_new, const float* const* d_prev, const adfl_slq_chunk* d_chunks,
+                        int64_t nchunks, int bits, const float* d_uniforms, const int64_t* d_ushift, uint64_t seed,
+                        uint64_t counter, void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels,
+                        int8_t* d_signs, float* d_norms, float* d_mins, void* stream) {
   if (int s = check_delta_args(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_workspace, workspace_bytes,
                                d_levels, d_signs, d_norms, d_mins))
     return s;
@@ -486,9 +552,43 @@ int adfl_rqsgd_encode_delta_batched(const float* const* d_new, const float* cons
   if (int s = launch_status()) return s;
   if (int s = adfl_stoch_detail::launch_finalize_linf(d_chunks, nchunks, d_workspace, d_norms, d_mins, st)) return s;
   const Uniforms U{d_uniforms, seed, counter};
-  hipLaunchKernelGGL(k_rqsgd_quantize_delta, grid, block, 0, st, d_new, d_prev, d_chunks,
-                     (float)((1LL << bits) - 1), (const float*)d_norms, d_ushift, U, d_levels, d_signs);
+  hipLaunchKernelGGL(k_rqsgd_quantize_delta<UPD>, grid, block, 0, st, d_new, d_prev, d_chunks,
+                     (float)((1LL << bits) - 1), (const float*)d_norms, (const float*)d_mins, d_ushift, U, d_levels,
+                     d_signs);
   return launch_status();
+}
+
+template <bool UPD>
+int rqsgd_delta_work(const float* const* d_new, const float* const* d_prev, const adfl_slq_chunk* d_chunks,
+                     int64_t nchunks, const int32_t* d_work, int64_t nwork, int bits, const float* d_uniforms,
+                     const int64_t* d_ushift, uint64_t seed, uint64_t counter, void* d_workspace,
+                     int64_t workspace_bytes, uint8_t* d_levels, int8_t* d_signs, float* d_norms, float* d_mins,
+                     void* stream) {
+  if (nwork == 0)
+    return rqsgd_delta_twopass<UPD>(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_ushift, seed, counter,
+                                    d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
+  if (!d_work || nwork < 0 || nwork > nchunks) return ADFL_E_ARG;
+  if (int s = check_delta_args(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_workspace, workspace_bytes,
+                               d_levels, d_signs, d_norms, d_mins))
+    return s;
+  const Uniforms U{d_uniforms, seed, counter};
+  hipLaunchKernelGGL(k_rqsgd_encode_delta_resident<UPD>, dim3((unsigned)nwork), dim3(kResBlock), 0,
+                     (hipStream_t)stream, d_new, d_prev, d_chunks, d_work, (float)((1LL << bits) - 1), d_ushift, U, d_levels,
+                     d_signs, d_norms, d_mins);
+  return launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+int adfl_rqsgd_encode_delta_batched(const float* const* d_new, const float* const* d_prev,
+                                    const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                    const float* d_uniforms, const int64_t* d_ushift, uint64_t seed, uint64_t counter,
+                                    void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels, int8_t* d_signs,
+                                    float* d_norms, float* d_mins, void* stream) {
+  return rqsgd_delta_twopass<false>(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_ushift, seed, counter,
+                                    d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
 }
 
 int adfl_rqsgd_encode_delta_batched_work(const float* const* d_new, const float* const* d_prev,
@@ -497,18 +597,29 @@ int adfl_rqsgd_encode_delta_batched_work(const float* const* d_new, const float*
                                          uint64_t seed, uint64_t counter, void* d_workspace, int64_t workspace_bytes,
                                          uint8_t* d_levels, int8_t* d_signs, float* d_norms, float* d_mins,
                                          void* stream) {
-  if (nwork == 0)
-    return adfl_rqsgd_encode_delta_batched(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_ushift, seed, counter,
-                                           d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
-  if (!d_work || nwork < 0 || nwork > nchunks) return ADFL_E_ARG;
-  if (int s = check_delta_args(d_new, d_prev, d_chunks, nchunks, bits, d_uniforms, d_workspace, workspace_bytes,
-                               d_levels, d_signs, d_norms, d_mins))
-    return s;
-  const Uniforms U{d_uniforms, seed, counter};
-  hipLaunchKernelGGL(k_rqsgd_encode_delta_resident, dim3((unsigned)nwork), dim3(kResBlock), 0, (hipStream_t)stream,
-                     d_new, d_prev, d_chunks, d_work, (float)((1LL << bits) - 1), d_ushift, U, d_levels, d_signs, d_norms,
-                     d_mins);
-  return launch_status();
+  return rqsgd_delta_work<false>(d_new, d_prev, d_chunks, nchunks, d_work, nwork, bits, d_uniforms, d_ushift, seed,
+                                 counter, d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
+}
+
+// The same encodes with d_hidden in prev's place, updated in place: h' = fp32(h + decode(stored bytes)).
+int adfl_rqsgd_encode_delta_update_batched(const float* const* d_new, float* const* d_hidden,
+                                           const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                           const float* d_uniforms, const int64_t* d_ushift, uint64_t seed,
+                                           uint64_t counter, void* d_workspace, int64_t workspace_bytes,
+                                           uint8_t* d_levels, int8_t* d_signs, float* d_norms, float* d_mins,
+                                           void* stream) {
+  return rqsgd_delta_twopass<true>(d_new, d_hidden, d_chunks, nchunks, bits, d_uniforms, d_ushift, seed, counter,
+                                   d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
+}
+
+int adfl_rqsgd_encode_delta_update_batched_work(const float* const* d_new, float* const* d_hidden,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                                int64_t nwork, int bits, const float* d_uniforms,
+                                                const int64_t* d_ushift, uint64_t seed, uint64_t counter,
+                                                void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels,
+                                                int8_t* d_signs, float* d_norms, float* d_mins, void* stream) {
+  return rqsgd_delta_work<true>(d_new, d_hidden, d_chunks, nchunks, d_work, nwork, bits, d_uniforms, d_ushift, seed,
+                                counter, d_workspace, workspace_bytes, d_levels, d_signs, d_norms, d_mins, stream);
 }
 
 }  // extern "C"

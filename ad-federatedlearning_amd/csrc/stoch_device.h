@@ -225,11 +225,17 @@ __device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
 // are loaded group by group.
 // pre (LDS, or null): Philox words generated ahead of time, group j's at pre[j * pre_stride]. s4 null: the
 // caller stores the sign bytes itself.
-template <int PB, class F, class E, class A>
+// post(j, k, live, q): called by every lane of the wave for each group the wave reaches, with the level dword q the
+// group stores (live lanes) — the hook of the encodes that also apply the stored bytes (it may hold a ballot).
+struct NoPost {
+  __device__ __forceinline__ void operator()(int, int, bool, uint32_t) const {}
+};
+
+template <int PB, class F, class E, class A, class P = NoPost>
 __device__ __forceinline__ void quantize_regs(const float4 (&v)[kPer], int tg, int n4, int64_t g0, const Uniforms& U,
                                               uint32_t* __restrict__ l4, uint32_t* __restrict__ s4, F fast, E exact,
                                               bool all_exact, A* acc, const uint4* pre = nullptr,
-                                              int pre_stride = 0) {
+                                              int pre_stride = 0, P post = P{}) {
   static_assert(kPer % PB == 0, "batches tile a chunk's groups");
 #pragma unroll
   for (int jb = 0; jb < kPer; jb += PB) {
@@ -267,7 +273,120 @@ __device__ __forceinline__ void quantize_regs(const float4 (&v)[kPer], int tg, i
         if (s4) s4[k] = pack4(sign_byte(v[j].x), sign_byte(v[j].y), sign_byte(v[j].z), sign_byte(v[j].w));
         if (acc) acc->add4(v[j]);
       }
+      post(j, k, live, q);
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// decoders (shared: stoch_codec.hip's decode kernels, and the encodes that also apply what they stored)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float pow2i(int k) {  // 2^k for k in [-126, 128] (128 -> inf), exact
+  return __uint_as_float((uint32_t)(k + 127) << 23);
+}
+
+
+// decoders (d divides by levels)
+__device__ __forceinline__ float qsgd_value_exact(uint32_t l, uint32_t sgn, float norm, float s) {
+  return __fdiv_rn(norm * (float)l, s) * (float)(int8_t)sgn;
+}
+
+__device__ __forceinline__ float qsgd_value_fast(uint32_t l, uint32_t sgn, float norm, const Div& d, bool& bad) {
+  return div_fast(norm * (float)l, d, bad) * (float)(int8_t)sgn;
+}
+
+__device__ __forceinline__ float rqsgd_value_exact(uint32_t l, uint32_t sgn, float norm, float mn, float s) {
+  const float sf = (float)(int8_t)sgn;
+  return l == 0u ? mn * sf : __fdiv_rn((norm * sf) * (float)l, s);
+}
+
+__device__ __forceinline__ float rqsgd_value_fast(uint32_t l, uint32_t sgn, float norm, float mn, const Div& d,
+                                                  bool& bad) {
+  const float sf = (float)(int8_t)sgn;
+  bool b2 = false;
+  const float v = div_fast((norm * sf) * (float)l, d, b2);
+  bad |= b2 & (l != 0u);
+  return l == 0u ? mn * sf : v;
+}
+
+__device__ __forceinline__ float cnat_value(uint32_t e, uint32_t sgn, float norm) {
+  const int k = (int)(int8_t)e;  // in [-128, 127]
+  // 2^k exactly: normal for k >= -126, the denormals 2^-127 / 2^-128 below
+  const float p = k >= -126 ? pow2i(k) : __uint_as_float(0x00400000u >> (-127 - k));
+  return (norm * (float)(int8_t)sgn) * p;
+}
+
+__device__ __forceinline__ void store4_nt(float4* p, float4 d) {
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  const f4v v = {d.x, d.y, d.z, d.w};
+  __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(p));
+}
+
+// Decoders. KIND 0 = QSGD, 1 = RQSGD, 2 = CNAT.
+template <int KIND>
+__device__ __forceinline__ float decode_exact(uint32_t l, uint32_t sgn, float norm, float mn, float s) {
+  if (KIND == 0) return qsgd_value_exact(l, sgn, norm, s);
+  if (KIND == 1) return rqsgd_value_exact(l, sgn, norm, mn, s);
+  return cnat_value(l, sgn, norm);
+}
+
+template <int KIND>
+__device__ __forceinline__ float decode_fast(uint32_t l, uint32_t sgn, float norm, float mn, const Div& d, bool& bad) {
+  if (KIND == 0) return qsgd_value_fast(l, sgn, norm, d, bad);
+  if (KIND == 1) return rqsgd_value_fast(l, sgn, norm, mn, d, bad);
+  return cnat_value(l, sgn, norm);
+}
+
+// Four decoded values from one dword of levels and one of signs. The fast division path falls back to the
+// exact one for the whole wave if any live lane's quotient is in doubt (every lane must call this).
+template <int KIND>
+__device__ __forceinline__ float4 decode4(uint32_t l, uint32_t g, float norm, float mn, const Div& d, float s,
+                                          bool live) {
+  bool bad = KIND != 2 && !d.fast;
+  float4 r;
+  r.x = decode_fast<KIND>(l & 0xffu, g & 0xffu, norm, mn, d, bad);
+  r.y = decode_fast<KIND>((l >> 8) & 0xffu, (g >> 8) & 0xffu, norm, mn, d, bad);
+  r.z = decode_fast<KIND>((l >> 16) & 0xffu, (g >> 16) & 0xffu, norm, mn, d, bad);
+  r.w = decode_fast<KIND>(l >> 24, g >> 24, norm, mn, d, bad);
+  if (KIND != 2 && wave_any(bad && live)) {
+    r.x = decode_exact<KIND>(l & 0xffu, g & 0xffu, norm, mn, s);
+    r.y = decode_exact<KIND>((l >> 8) & 0xffu, (g >> 8) & 0xffu, norm, mn, s);
+    r.z = decode_exact<KIND>((l >> 16) & 0xffu, (g >> 16) & 0xffu, norm, mn, s);
+    r.w = decode_exact<KIND>(l >> 24, g >> 24, norm, mn, s);
+  }
+  return r;
+}
+
+// The 4 sign bytes of a float4 group as the sign plane's dword.
+__device__ __forceinline__ uint32_t sign4(const float4& x) {
+  return pack4(sign_byte(x.x), sign_byte(x.y), sign_byte(x.z), sign_byte(x.w));
+}
+
+// h' = fp32(h + d) for one 4-element group of a hidden tensor: a 16-byte store where the group's address allows it
+// (vec, block-uniform), four 4-byte stores otherwise; the same bits either way. The 16-byte store is non-temporal
+// when kStochHiddenNt (slq_delta.hip's switch: the next broadcast reads h only after a whole buffer of client
+// updates; DESIGN.md §10 has the A/B for these kernels).
+#ifndef ADFL_UPDATE_H_NT
+#define ADFL_UPDATE_H_NT 1
+#endif
+constexpr bool kStochHiddenNt = ADFL_UPDATE_H_NT != 0;
+
+__device__ __forceinline__ float4 load_h4(const float* p, bool vec) {
+  if (vec) return *reinterpret_cast<const float4*>(p);
+  return make_float4(p[0], p[1], p[2], p[3]);
+}
+
+__device__ __forceinline__ void store_sum_h4(float* p, bool vec, const float4& h, const float4& d) {
+  const float4 r = make_float4(h.x + d.x, h.y + d.y, h.z + d.z, h.w + d.w);
+  if (vec && kStochHiddenNt) {
+    store4_nt(reinterpret_cast<float4*>(p), r);
+  } else if (vec) {
+    *reinterpret_cast<float4*>(p) = r;
+  } else {
+    p[0] = r.x;
+    p[1] = r.y;
+    p[2] = r.z;
+    p[3] = r.w;
   }
 }
 

@@ -234,6 +234,38 @@ int adfl_rqsgd_encode_delta_batched_work(const float* const* d_new, const float*
 int adfl_bucket_diff(float* d_out, const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* const* d_new,
                      const float* const* d_prev, void* stream);
 
+/* ---- QAFeL's broadcast (Src/ADFL/Server/qafel.py:156-180): the delta encode of g - h that also leaves
+ * h' = fp32(h + d) in the hidden tensors, d being the codec's decode of the bytes the call stored (the level byte
+ * after its uint8 wraparound, the sign byte, the tensor's fp32 norm, RQSGD's min factor; the decode kernels' own
+ * arithmetic). A tensor whose norm is 0 decodes to +0, which is still added (a hidden -0 becomes +0); a NaN norm
+ * makes the whole hidden tensor NaN. Bit-identical to the encode followed by the codec's decode and an fp32 add.
+ * d_hidden: one fp32 pointer per tensor, addressed as the delta sources are; the tensors are written in place, must
+ * not overlap d_new's, the planes or each other, and have no alignment precondition (16-byte accesses where the
+ * address allows, 4-byte ones otherwise, the same bits). Additions: ADFL_SLQ_ABI_VERSION is unchanged.
+ *
+ * RQSGD: adfl_rqsgd_encode_delta_batched[_work] with d_hidden in d_prev's place — the same arguments, outputs
+ * (bit for bit) and errors; 22 bytes per element for the two passes, 18 for the one launch. */
+int adfl_rqsgd_encode_delta_update_batched(const float* const* d_new, float* const* d_hidden,
+                                           const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                           const float* d_uniforms, const int64_t* d_ushift, uint64_t seed,
+                                           uint64_t counter, void* d_workspace, int64_t workspace_bytes,
+                                           uint8_t* d_levels, int8_t* d_signs, float* d_norms, float* d_mins,
+                                           void* stream);
+int adfl_rqsgd_encode_delta_update_batched_work(const float* const* d_new, float* const* d_hidden,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks, const int32_t* d_work,
+                                                int64_t nwork, int bits, const float* d_uniforms,
+                                                const int64_t* d_ushift, uint64_t seed, uint64_t counter,
+                                                void* d_workspace, int64_t workspace_bytes, uint8_t* d_levels,
+                                                int8_t* d_signs, float* d_norms, float* d_mins, void* stream);
+
+/* QSGD from given norms (the reference-order norm of the difference bucket d_x = g - h, adfl_bucket_diff's
+ * output): adfl_qsgd_quantize_batched's planes, plus the update of d_hidden (ntensors pointers); 14 bytes per
+ * element. Errors as adfl_qsgd_quantize_batched, and ADFL_E_ARG for a null d_hidden or ntensors < 1. */
+int adfl_qsgd_quantize_update_batched(const float* d_x, const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                      const float* d_norms, const float* d_uniforms, uint64_t seed, uint64_t counter,
+                                      uint8_t* d_levels, int8_t* d_signs, float* const* d_hidden, int64_t ntensors,
+                                      void* stream);
+
 /* The Philox uniforms the codecs draw: d_out[i] = u(start + i) of stream (seed, counter), i < n.
  * (Exposed for tests and for callers that want the uniforms a call used.) */
 int adfl_philox_uniforms(float* d_out, int64_t n, int64_t start, uint64_t seed, uint64_t counter, void* stream);

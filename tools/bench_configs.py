@@ -31,6 +31,9 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             reference's statements run by torch on the same device tensors in the same process (FedBuff 4 launches
             per tensor, FADAS 10); HIP events, Infinity Cache read-flushed before every call, medians of --steps
             calls, three repeats; parity against the numpy restatement (tests/flush_cases.py); no threshold
+  broadcast_stoch  QAFeL's broadcast through the stochastic channels on the C3 layouts and one 2^28-element tensor
+            (the protocol of `broadcast`): per codec broadcast_delta_ against send_delta + receive_add_ (wall), and in
+            HIP events each fused kernel against the kernels it replaces over planes that stay on the device
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -1402,6 +1405,220 @@ def mode_broadcast(args, world, rank, dev):
     return line
 
 
+def _broadcast_stoch_leg(sizes, args, dev, junk, repeats=3):
+    """One layout of the broadcast_stoch leg (mode_broadcast's protocol per stochastic codec), hidden state and g
+    both device-resident, bits 8.
+
+    Kernels alone (HIP events, the Infinity Cache read-flushed before every call), each new kernel against the sum
+    of the kernels it replaces over planes that stay on the device: rqsgd_encode_delta_update_batched (two passes
+    and, where the layout allows it, one launch) against rqsgd_encode_delta_batched + dequantize_axpby_batched;
+    qsgd_quantize_update_batched against qsgd_quantize_batched + dequantize_axpby_batched (the difference bucket
+    and its norms made once: that part is unchanged code). Whole call (wall), per codec: broadcast_delta_ against
+    send_delta + receive_add_; the fused route counts as faster when its median lies below the two calls' median
+    by more than the two calls' own spread across the repeats (max - min of their `repeats` medians).
+
+    A broadcast pulls h onto g, and a tensor whose difference has become exactly zero takes the codecs' norm == 0
+    branch, which reads less: successive calls therefore alternate between two g (as the server's model moves
+    between two flushes), so every timed call encodes a difference of the magnitude of the step between them."""
+    import numpy as np
+    from adfl_amd import _lib, ops
+    from adfl_amd import stoch as sops
+    from adfl_amd.Channel import CNATChannel, QSGDChannel, RQSGDChannel
+    gen = torch.Generator(device=dev).manual_seed(0)
+    hidden, new = {}, {}
+    for i, n in enumerate(sizes):
+        for name, shape in ((f"layer{i:03d}.weight", (1, n)), (f"layer{i:03d}.bias", (64,))):
+            new[name] = torch.randn(shape, device=dev, generator=gen) * 1e-2
+            hidden[name] = new[name] + torch.randn(shape, device=dev, generator=gen) * 1e-5
+    new2 = {k: v + torch.randn(v.shape, device=dev, generator=gen) * 1e-5 for k, v in new.items()}
+    news = (new, new2)
+    names = [k for k in hidden if hidden[k].ndim > 1]
+    gs, gs2, hs = [new[k] for k in names], [new2[k] for k in names], [hidden[k].clone() for k in names]
+    comp, lay = ops.BucketLayout(list(sizes), align=1), ops.BucketLayout(list(sizes))
+    ushift = np.ascontiguousarray(comp.offsets - lay.offsets, dtype=np.int64)
+    table = lambda ts: torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64)   # noqa: E731
+    h_tab = table(hs)
+    g_alt = ((gs, (table(gs), h_tab)), (gs2, (table(gs2), h_tab)))   # (g, its pointer tables) of even / odd calls
+    calls = [0]
+
+    def next_g():
+        calls[0] += 1
+        return g_alt[calls[0] & 1]
+    n = int(sum(sizes))
+    resident_ok = lay.nwork > 0 and lay.max_tensor_chunks <= _lib.DELTA_RESIDENT_CHUNKS
+    same = lambda a, b: torch.equal(a.view(torch.int32), b.view(torch.int32))   # noqa: E731
+
+    def owned(L):
+        m = torch.zeros(L.total, dtype=torch.bool, device=dev)
+        for o, k in zip(L.offsets.tolist(), sizes):
+            m[o:o + k] = True
+        return m
+
+    def events(step):
+        out = []
+        for _ in range(repeats):
+            _, evs = timed(step, args.steps, args.warmup, 1, 2)
+            out.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+        return out
+
+    def kernel(fn):
+        def step(ev):
+            junk.amax()   # read-flush of the Infinity Cache
+            if ev is not None:
+                ev[0].record()
+            fn()
+            if ev is not None:
+                ev[1].record()
+        return step
+
+    def record(res, key, f, pair, nbytes):
+        res[f"{key}_alone_ms"] = round(_median(f), 4)
+        res[f"{key}_alone_ms_repeats"] = [round(v, 4) for v in f]
+        res[f"{key}_below_pair_by_more_than_spread"] = bool(_median(pair) - _median(f) > max(pair) - min(pair))
+        res[f"{key}_over_pair"] = round(_median(f) / _median(pair), 4)
+        res[f"{key}_frac_of_peak_on_{nbytes}B"] = round(nbytes * n / (_median(f) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+
+    res = {"tensors": len(sizes), "elements": n}
+    # ---- RQSGD: planes in the aligned bucket, the compact draws kept by ushift (the channel's layout)
+    lv, sg = torch.empty(lay.total, dtype=torch.uint8, device=dev), torch.empty(lay.total, dtype=torch.int8, device=dev)
+    norms, mins = torch.empty(lay.ntensors, device=dev), torch.empty(lay.ntensors, device=dev)
+    ws = sops.workspace(lay, dev)
+    kw = dict(ushift=ushift, seed=11, counter=0, levels=lv, signs=sg, norms=norms, mins=mins, ws=ws)
+
+    def rq_pair(h, g=gs, **k):
+        out = sops.rqsgd_encode_delta_batched(g, h, lay, 8, **k)
+        sops.dequantize_axpby_batched("rqsgd", out[0], out[1], out[2], lay, 8, [h], [h], 1.0, 1.0, mins=out[3])
+        return out
+    x = ops.bucket_diff(gs, hs, comp)   # QSGD's difference bucket, before the timed calls move hs
+    want_h = [t.clone() for t in hs]
+    want = [t.clone() for t in rq_pair(want_h, ushift=ushift, seed=11, counter=0)]
+    m = owned(lay)
+    rq = {"parity": {}}
+    forms = (("twopass", False), ("resident", True)) if resident_ok else (("twopass", False),)
+    for form, resident in forms:
+        got_h = [t.clone() for t in hs]
+        got = sops.rqsgd_encode_delta_update_batched(gs, got_h, lay, 8, ushift=ushift, seed=11, counter=0,
+                                                     resident=resident)
+        rq["parity"][form] = bool(torch.equal(got[0][m], want[0][m]) and torch.equal(got[1][m], want[1][m])
+                                  and same(got[2], want[2]) and same(got[3], want[3])
+                                  and all(same(a, b) for a, b in zip(got_h, want_h)))
+    del want_h, want, got_h, got
+    def rq_pair_step():
+        g, tabs = next_g()
+        rq_pair(hs, g, ptrs=tabs, **kw)
+
+    def rq_fused_step(resident):
+        g, tabs = next_g()
+        sops.rqsgd_encode_delta_update_batched(g, hs, lay, 8, resident=resident, ptrs=tabs, **kw)
+    pair = events(kernel(rq_pair_step))
+    rq["pair_alone_ms"], rq["pair_alone_ms_repeats"] = round(_median(pair), 4), [round(v, 4) for v in pair]
+    for form, resident in forms:
+        f = events(kernel(lambda: rq_fused_step(resident)))
+        record(rq, f"fused_{form}", f, pair, 18 if resident else 22)
+    rq["zero_norm_tensors_after_timing"] = int((norms == 0).sum())
+    res["rqsgd"] = rq
+    # ---- QSGD under the reference norm: the compact difference bucket and its norms made once
+    qn = sops.torch_norms(x, comp)
+    lvc, sgc = lv[:comp.total], sg[:comp.total]
+    qkw = dict(seed=11, counter=0, levels=lvc, signs=sgc)
+
+    def qs_pair(h, **k):
+        a, b = sops.qsgd_quantize_batched(x, comp, 8, qn, **k)
+        sops.dequantize_axpby_batched("qsgd", a, b, qn, comp, 8, [h], [h], 1.0, 1.0)
+        return a, b
+    hs = [hidden[k].clone() for k in names]   # (x and its norms do not move: neither do the kernels' paths)
+    h_tab = table(hs)
+    want_h, got_h = [t.clone() for t in hs], [t.clone() for t in hs]
+    want = [t.clone() for t in qs_pair(want_h, seed=11, counter=0)]
+    got = sops.qsgd_quantize_update_batched(x, comp, 8, qn, got_h, seed=11, counter=0)
+    qs = {"parity": bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+                         and all(same(a, b) for a, b in zip(got_h, want_h))),
+          "zero_norm_tensors": int((qn == 0).sum())}
+    del want_h, want, got_h, got
+    pair = events(kernel(lambda: qs_pair(hs, **qkw)))
+    qs["pair_alone_ms"], qs["pair_alone_ms_repeats"] = round(_median(pair), 4), [round(v, 4) for v in pair]
+    f = events(kernel(lambda: sops.qsgd_quantize_update_batched(x, comp, 8, qn, hs, ptrs=h_tab, **qkw)))
+    record(qs, "fused", f, pair, 14)
+    res["qsgd"] = qs
+    del x, lv, sg
+
+    # ---- the whole call, wall clock, per codec
+    def wall(fn):
+        out = []
+        for _ in range(args.steps):
+            junk.amax()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return _median(out)
+
+    for codec, cls in (("qsgd", QSGDChannel), ("rqsgd", RQSGDChannel), ("cnat", CNATChannel)):
+        ch = cls(8)
+
+        def two_calls(h, g):
+            c = ch.send_delta(h, g)[0]
+            ch.receive_add_(c, [h])
+            return c
+
+        def next_new():
+            calls[0] += 1
+            return news[calls[0] & 1]
+        h_a, h_b = ({k: v.clone() for k, v in hidden.items()} for _ in range(2))
+        torch.manual_seed(3)
+        c_a = ch.broadcast_delta_(h_a, new)[0]
+        torch.manual_seed(3)
+        c_b = two_calls(h_b, new)
+        call = {"call_parity": bool(_stoch_same(c_a, c_b) and all(same(h_a[k], h_b[k]) for k in h_a))}
+        del c_a, c_b
+        for _ in range(args.warmup):
+            ch.broadcast_delta_(h_a, next_new()), two_calls(h_b, next_new())
+        f_ms = [wall(lambda: ch.broadcast_delta_(h_a, next_new())) for _ in range(repeats)]
+        u_ms = [wall(lambda: two_calls(h_b, next_new())) for _ in range(repeats)]
+        call["zero_norm_payloads_in_last_call"] = sum(
+            isinstance(p.scale, torch.Tensor) for p in ch.broadcast_delta_(h_a, next_new())[0].params.values())
+        call.update({"broadcast_delta_ms": round(_median(f_ms), 4),
+                     "broadcast_delta_ms_repeats": [round(v, 4) for v in f_ms],
+                     "send_delta_receive_add_ms": round(_median(u_ms), 4),
+                     "send_delta_receive_add_ms_repeats": [round(v, 4) for v in u_ms],
+                     "two_calls_spread_ms": round(max(u_ms) - min(u_ms), 4),
+                     "call_below_two_calls_by_more_than_spread":
+                         bool(_median(u_ms) - _median(f_ms) > max(u_ms) - min(u_ms))})
+        res.setdefault(codec, {}).update(call)
+        del h_a, h_b
+    return res
+
+
+def mode_broadcast_stoch(args, world, rank, dev):
+    """QAFeL's broadcast through QSGDChannel / RQSGDChannel / CNATChannel(8) (the hidden-state update fused into
+    the delta encode) against the two calls it replaces, on the C3 layouts and one 2^28-element tensor; written to
+    profiles/broadcast/broadcast_stoch.json (an A/B library selected with ADFL_LIB_VARIANT writes
+    broadcast_stoch_<its name>.json: the h' store flavour)."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    legs = {"c3_equal": _broadcast_stoch_leg(recipes.bucket_sizes("equal"), args, dev, junk),
+            "c3_loguniform": _broadcast_stoch_leg(recipes.bucket_sizes("loguniform", 0), args, dev, junk),
+            "one_tensor_2p28": _broadcast_stoch_leg([1 << 28], args, dev, junk)}
+    variant = os.environ.get("ADFL_LIB_VARIANT")
+    parity = all(all(leg["rqsgd"]["parity"].values()) and leg["qsgd"]["parity"]
+                 and all(leg[c]["call_parity"] for c in ("qsgd", "rqsgd", "cnat")) for leg in legs.values())
+    line = {"mode": "broadcast_stoch", "metric": "RQSGD fused delta encode + hidden-state update, kernels alone, C3 "
+            "equal layout, Infinity Cache flushed", "unit": "ms",
+            "library": os.path.basename(variant) if variant else "product",
+            "value": min(v for k, v in legs["c3_equal"]["rqsgd"].items()
+                         if k.startswith("fused_") and k.endswith("_alone_ms")),
+            "parity": parity, "steps": args.steps, "repeats": 3, **legs}
+    out_dir = os.path.join(REPO, "profiles", "broadcast")
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if not variant else "_" + os.path.splitext(os.path.basename(variant))[0].replace("libadfl_", "")
+    with open(os.path.join(out_dir, f"broadcast_stoch{tag}.json"), "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    return line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1409,7 +1626,8 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta", "delta_stoch", "apply", "flush", "broadcast"], required=True)
+                                      "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch"],
+                   required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
@@ -1427,7 +1645,7 @@ def main():
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
-            "flush": mode_flush, "broadcast": mode_broadcast}[args.mode](
+            "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
