@@ -1,7 +1,7 @@
 """What the SLQ channels (quant.py) and the stochastic channels (stoch.py) share above the staging layer:
 ``_CodecChannel``, the class skeleton of a bi-directional codec channel (the reference's six-method surface,
-``receive_add_``, ``receive_mean`` and the asynchronous server's ``receive_axpby`` / ``receive_scaled`` /
-``receive_scaled_add_`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
+``receive_add_``, ``receive_mean``, the synchronous DELTA server's ``receive_mean_axpby`` and the asynchronous
+server's ``receive_axpby`` / ``receive_scaled`` / ``receive_scaled_add_`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
 uni-directional variants; and the host aggregate of the entries no device kernel takes (``_aggregate_entries``,
 ``device_mean_order_ok``).
 
@@ -146,6 +146,8 @@ class _CodecChannel(Channel):
       when the updates are anything else (they are then classified entry by entry, with the hooks below);
     * ``_fusable(p)``: an entry the decode-mean launch takes; ``_mean_shape(p)``: its decoded shape (one shape
       across the updates fuses); ``_mean_payloads(all_c_params, names)``: the means of such entries;
+    * ``_mean_host_classify(all_c_params, names)`` and ``_mean_apply(...)``: that classification without the launch,
+      and the fused decode-mean + axpby over such entries and their base tensors (receive_mean_axpby);
     * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor;
     * ``_apply_payload(c_params, names, st)``: the ``_fusable`` entries' payloads staged on the device and the
       codec's fused decode + axpby over them — what receive_axpby, receive_scaled and receive_scaled_add_ (the
@@ -260,8 +262,7 @@ class _CodecChannel(Channel):
             fused, decoded, plain = fast
             out.update(zip(fused, decoded))
         else:
-            fused = [n for n in names if all(n in c.params and self._fusable(c.params[n]) for c in all_c_params)
-                     and len({tuple(self._mean_shape(c.params[n])) for c in all_c_params}) == 1] if order_ok else []
+            fused = self._mean_fused_names(all_c_params, names) if order_ok else []
             if fused:
                 out.update(zip(fused, self._mean_payloads(all_c_params, fused)))
         rest = [n for n in names if n not in out]
@@ -280,6 +281,77 @@ class _CodecChannel(Channel):
                 parts.append(part)
             out.update(_aggregate_entries(rest, parts))
         return {n: out[n] for n in names}, time.perf_counter() - s_time
+
+    def _mean_fused_names(self, all_c_params: List[QuantParameters], names: List[str]) -> List[str]:
+        """The entries the decode-mean launch takes: ``_fusable`` in every update, one decoded shape."""
+        return [n for n in names if all(n in c.params and self._fusable(c.params[n]) for c in all_c_params)
+                and len({tuple(self._mean_shape(c.params[n])) for c in all_c_params}) == 1]
+
+    # -- the synchronous DELTA server's step: decode-mean + axpby ---------------------------------------------
+    def receive_mean_axpby(self, all_c_params: List[CompressedParameters], base: Parameters, alpha: float = 1.0,
+                           beta: float = 1.0) -> Tuple[Parameters, float]:
+        """``add_parameters(base, simple_aggregate([self.on_server_receive(c)[0] for c in all_c_params]), alpha,
+        beta)`` — ``Simple(CommType.DELTA, sync=True)._sync_update`` with (1.0, 1.0)
+        (Src/ADFL/Strategy/simple.py:87-89 over Src/ADFL/model.py:221-234,326-334), bit-identical to it: per element
+        fp32(fp32(alpha * base) + fp32(beta * mean)), the mean as ``receive_mean`` computes it. Returns (new
+        parameters, seconds); keys in the first update's order, `base` and the payloads unmodified, every returned
+        tensor its own storage, living where its base entry lives.
+
+        An entry ``receive_mean`` would average on the device (``_fusable`` in every update, one shape, torch's
+        sum order as the kernels restate it) whose base tensor is fp32, contiguous, 16-byte aligned and of the
+        decoded shape is decoded, averaged and combined by one launch (``_mean_apply``): the K payloads and the
+        base are read once, no mean is written. Bases on the staging device are read in place; CPU bases (ADFL's
+        own pattern) are staged by one H2D into a bucket of the mean's layout and come back as owned CPU tensors.
+        Every other entry takes ``receive_mean``, then the reference's statement ``(alpha * base) + (beta *
+        mean)``, so dtype promotion is torch's (the int64 counter comes back fp32)."""
+        if not all_c_params:
+            raise AssertionError("receive_mean_axpby: no updates")   # simple_aggregate asserts len > 0
+        for c in all_c_params:
+            assert isinstance(c, QuantParameters)
+        names = list(all_c_params[0].params.keys())
+        assert set(base.keys()) == set(names)   # add_parameters, model.py:327
+        s_time = time.perf_counter()
+        out: Parameters = {}
+        if device_mean_order_ok() and torch.cuda.is_available():
+            cls = self._mean_host_classify(all_c_params, names)
+            fused = cls[0] if cls is not None else self._mean_fused_names(all_c_params, names)
+            dev_idx = torch.cuda.current_device()
+            groups: Dict[str, List[str]] = {"cuda": [], "cpu": []}
+            for n in fused:
+                t = base[n]
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.data_ptr() % 16 == 0
+                        and t.shape == torch.Size(self._mean_shape(all_c_params[0].params[n]))):
+                    continue
+                if t.is_cuda and t.device.index == dev_idx:
+                    groups["cuda"].append(n)
+                elif not t.is_cuda:
+                    groups["cpu"].append(n)
+            for where, ns in groups.items():
+                if ns:
+                    host = cls if cls is not None and len(ns) == len(cls[0]) else None
+                    out.update(zip(ns, self._mean_apply(all_c_params, ns, [base[n] for n in ns], where, alpha, beta,
+                                                        host)))
+        rest = {n for n in names if n not in out}
+        if rest:
+            agg, _ = self.receive_mean([QuantParameters({n: p for n, p in c.params.items() if n in rest}, 0)
+                                        for c in all_c_params])
+            with torch.no_grad():
+                for n, m in agg.items():
+                    out[n] = (alpha * base[n]) + (beta * m.to(base[n].device))
+        return {n: out[n] for n in names}, time.perf_counter() - s_time
+
+    def _mean_host_classify(self, all_c_params: List[QuantParameters], names: List[str]):
+        """``_mean_host_updates``' classification without its launch, where a codec has one in native calls:
+        (fused names, ...the codec's own staging arguments) for K CPU updates of one model, else None."""
+        return None
+
+    def _mean_apply(self, all_c_params: List[QuantParameters], names: List[str], bases: List[torch.Tensor],
+                    where: str, alpha: float, beta: float, host) -> List[torch.Tensor]:
+        """The fused decode-mean + axpby over the entries `names` (``_mean_fused_names``' kind) and their base
+        tensors, all on the staging device (where == "cuda") or all on the CPU ("cpu"): one new owned tensor per
+        entry, where its base lives. host: ``_mean_host_classify``'s result when it covers exactly `names`."""
+        raise NotImplementedError
 
     # -- the asynchronous server's update step: decode + axpby / scale ---------------------------------------
     def receive_axpby(self, c_params: CompressedParameters, base: Parameters, alpha: float,
@@ -437,6 +509,27 @@ def _apply_fused(channel: "_CodecChannel", c_params: QuantParameters, names: Lis
             else:
                 outs = _hand_out(out_dev, lay, shapes, [True] * len(names), st, "ax_out")
     return outs
+
+
+def _mean_axpby_out(st, lay: ops.BucketLayout, shapes, bases: List[torch.Tensor], where: str, key: str, launch,
+                    like=None) -> List[torch.Tensor]:
+    """The output side of a fused decode-mean + axpby whose payload rows are staged (``_mean_apply``):
+    launch(bases, outs) runs the codec's kernel over ops.dequantize_mean_axpby_batched's bases / outs.
+      where == "cuda": pointer tables straight to the base tensors and to new device tensors;
+      where == "cpu":  the bases staged by one H2D into a bucket of the rows' element layout, one launch over the
+                       two flat buckets, the result handed out as owned CPU tensors (`like`: as _hand_out)."""
+    dev = st.device
+    with torch.no_grad():
+        if where == "cuda":
+            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+            launch(bases, outs)
+            # the next call's host gather rewrites the pinned staging this call's H2D reads from
+            torch.cuda.current_stream(dev).synchronize()
+            return outs
+        base_dev = _stage_in(bases, lay, st, "ma_base", torch.float32)
+        out_dev = st.buf(key, lay.total, torch.float32)
+        launch(base_dev, out_dev)
+        return _hand_out(out_dev, lay, shapes, [True] * len(bases), st, key, like=like)
 
 
 class _Unidirectional:

@@ -37,7 +37,8 @@ from .. import _lib, _torchhost, hostcopy, ops, qerror
 from .._lib import check
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
 from . import _staging as _stg
-from ._base import _broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle, _Unidirectional
+from ._base import (_broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _mean_axpby_out, _passthrough_idle,
+                    _Unidirectional)
 from ._staging import (_DeviceStaging, _PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _int8_view, _ph,
                        _plan, _range_copies, _ranges, _rows_from_ptrs, _serialized, _stage_in, _stage_rows,
                        _staging, phase_clock)  # noqa: F401  (phase_clock: re-exported, bench.py uses it from here)
@@ -400,11 +401,13 @@ def _decode_add(c_params: QuantParameters, names: List[str], targets: List[Param
 
 @_serialized
 def _decode_mean(clients: List[List[torch.Tensor]], scales: List[List[float]], shapes: List[torch.Size],
-                 packed: bool) -> List[torch.Tensor]:
+                 packed: bool, apply=None) -> List[torch.Tensor]:
     """The fp32 mean over K clients of their decoded tensors, tensor by tensor, in torch's CPU summation
     order for simple_aggregate (csrc/torch_sum_order.h), in ONE launch (ops.dequantize_mean_batched): clients[k][j] is client k's payload for tensor j (a qint8 tensor,
     or ceil(n/2) packed int8 bytes with packed=True), scales[k][j] its scale. Returns one
-    owned tensor per entry (CPU when every client's payload is on the CPU)."""
+    owned tensor per entry (CPU when every client's payload is on the CPU). apply = (bases, where, alpha, beta):
+    the fused decode-mean + axpby over the same rows instead (_mean_axpby_out), one owned tensor per entry where
+    its base lives."""
     st = _staging()
     dev = st.device
     sizes = tuple(int(torch.Size(s).numel()) for s in shapes)
@@ -415,6 +418,12 @@ def _decode_mean(clients: List[List[torch.Tensor]], scales: List[List[float]], s
         lay = b_lay = st.layout(sizes, align=1)
     rows = _stage_rows(clients, b_lay, st, "mq")
     s_dev = torch.tensor(scales, dtype=torch.float32).to(dev, non_blocking=True)
+    if apply is not None:
+        bases, where, alpha, beta = apply
+        return _mean_axpby_out(st, lay, [torch.Size(s) for s in shapes], bases, where, "m_out",
+                               lambda b, o: ops.dequantize_mean_axpby_batched(
+                                   rows if packed else rows.view(torch.int8), s_dev, lay, b, o, alpha, beta,
+                                   packed=packed))
     out_dev = ops.dequantize_mean_batched(rows if packed else rows.view(torch.int8), s_dev, lay,
                                           out=st.buf("m_out", lay.total, torch.float32), packed=packed)
     on_cpu = [not any(c[j].is_cuda for c in clients) for j in range(len(sizes))]
@@ -423,16 +432,21 @@ def _decode_mean(clients: List[List[torch.Tensor]], scales: List[List[float]], s
 
 @_serialized
 def _decode_mean_host(st: _DeviceStaging, like: List[torch.Tensor], numel: torch.Tensor, ptrs: List[np.ndarray],
-                      scales: torch.Tensor) -> List[torch.Tensor]:
+                      scales: torch.Tensor, apply=None) -> List[torch.Tensor]:
     """_decode_mean for K CPU qint8 payload lists already checked (SLQChannel._mean_host_updates): each client's
     bytes gathered straight from the storages into its pinned row (_rows_from_ptrs), one decode-mean launch,
     and the fp32 means handed back as owned CPU tensors shaped like `like`, created by one native call per
-    staging range while the D2H runs."""
+    staging range while the D2H runs. apply: as _decode_mean's."""
     dev = st.device
     lay = st.layout(tuple(numel.tolist()), align=1)
     _host_heap(lay)
     rows = _rows_from_ptrs(ptrs, lay, st, "mq")
     s_dev = scales.to(dev, non_blocking=True)
+    if apply is not None:
+        bases, where, alpha, beta = apply
+        return _mean_axpby_out(st, lay, [q.shape for q in like], bases, where, "m_out",
+                               lambda b, o: ops.dequantize_mean_axpby_batched(rows.view(torch.int8), s_dev, lay, b, o,
+                                                                              alpha, beta), like=like)
     out_dev = ops.dequantize_mean_batched(rows.view(torch.int8), s_dev, lay,
                                           out=st.buf("m_out", lay.total, torch.float32))
     return _hand_out(out_dev, lay, [None] * len(like), [True] * len(like), st, "m_out", like=like)
@@ -672,6 +686,18 @@ class SLQChannel(_CodecChannel):
         decode-mean launch over rows staged straight from the payloads' storages, the outputs created by one
         native call per staging range — or None when the updates are anything else (receive_mean then
         classifies entry by entry)."""
+        cls = SLQChannel._mean_host_classify(all_c_params, names)
+        if cls is None:
+            return None
+        fused, plain, like, numel, ptrs, scales = cls
+        if not fused:
+            return [], [], plain
+        return fused, _decode_mean_host(_staging(), like, numel, ptrs, scales), plain
+
+    @staticmethod
+    def _mean_host_classify(all_c_params: List[QuantParameters], names: List[str]):
+        """_mean_host_updates' classification: (fused names, the ndim <= 1 names, the first update's fused
+        payloads, their element counts, every update's payload pointers, the [K, T] fp32 scales), or None."""
         if any(list(c.params.keys()) != names for c in all_c_params):
             return None
         th = _torchhost.get()
@@ -682,7 +708,7 @@ class SLQChannel(_CodecChannel):
         idx = np.nonzero(kinds[0] == 1)[0].tolist()
         plain = [names[i] for i in np.nonzero(kinds[0] == 0)[0].tolist()]   # ndim <= 1 in every update
         if not idx:
-            return [], [], plain
+            return [], plain, [], None, [], None
         qs = [[d[i] for i in idx] for d in datas]
         metas = [th.qint8_meta(q) for q in qs]   # (ok, all contiguous CPU, numel, fp32 scales, data pointers)
         numel = metas[0][2]
@@ -690,10 +716,18 @@ class SLQChannel(_CodecChannel):
             return None
         if not th.shapes_equal(qs):
             return None
-        fused = [names[i] for i in idx]
-        st = _staging()
-        return fused, _decode_mean_host(st, qs[0], numel, [m[4].numpy().view(np.uint64) for m in metas],
-                                        torch.stack([m[3] for m in metas])), plain
+        return ([names[i] for i in idx], plain, qs[0], numel, [m[4].numpy().view(np.uint64) for m in metas],
+                torch.stack([m[3] for m in metas]))
+
+    def _mean_apply(self, all_c_params: List[QuantParameters], names: List[str], bases: List[torch.Tensor],
+                    where: str, alpha: float, beta: float, host) -> List[torch.Tensor]:
+        apply = (bases, where, alpha, beta)
+        if host is not None:   # K CPU updates, classified natively: rows staged straight from the storages
+            _, _, like, numel, ptrs, scales = host
+            return _decode_mean_host(_staging(), like, numel, ptrs, scales, apply=apply)
+        qs = [[c.params[n].data for n in names] for c in all_c_params]
+        return _decode_mean(qs, [[q.q_scale() for q in c] for c in qs], [q.shape for q in qs[0]], packed=False,
+                            apply=apply)
 
     @staticmethod
     def _passthrough(p: QuantParameter) -> bool:
@@ -897,10 +931,20 @@ class PackedSLQChannel(SLQChannel):
         classification of SLQChannel's qint8 updates does not apply (receive_mean classifies entry by entry)."""
         return None
 
+    @staticmethod
+    def _mean_host_classify(all_c_params: List[QuantParameters], names: List[str]):
+        return None
+
     def _mean_payloads(self, all_c_params: List[QuantParameters], names: List[str]) -> List[torch.Tensor]:
+        return self._mean_apply(all_c_params, names, None, None, 1.0, 1.0, None)
+
+    def _mean_apply(self, all_c_params: List[QuantParameters], names: List[str], bases, where, alpha: float,
+                    beta: float, host) -> List[torch.Tensor]:
+        """bases None: the plain mean (_mean_payloads)."""
         return _decode_mean([[c.params[n].data for n in names] for c in all_c_params],
                             [[c.params[n].scale for n in names] for c in all_c_params],
-                            [torch.Size(all_c_params[0].params[n].shape) for n in names], packed=True)
+                            [torch.Size(all_c_params[0].params[n].shape) for n in names], packed=True,
+                            apply=None if bases is None else (bases, where, alpha, beta))
 
     _PACKED_DELTA = True
 

@@ -50,8 +50,8 @@ from .. import stoch as sops
 from .._lib import check
 from ..model import CompressedParameters, Parameters, QuantParameter, QuantParameters
 from . import _staging as _stg
-from ._base import (_broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _passthrough_idle,
-                    _Unidirectional)
+from ._base import (_broadcast_groups, _CodecChannel, _delta_on_device, _delta_pairs, _mean_axpby_out,
+                    _passthrough_idle, _Unidirectional)
 from ._staging import (_PendingD2H, _chunk_meta, _drain, _hand_out, _host_heap, _ph, _range_copies, _ranges,
                        _rows_from_ptrs, _serialized, _stage_in, _stage_rows, _staging)
 
@@ -766,10 +766,12 @@ def _decode_stoch_bucket(st, items: List[Tuple[str, QuantParameter]], codec: str
 
 @_serialized
 def _decode_mean_stoch(all_c_params: List[QuantParameters], names: List[str], codec: str,
-                       bits: int) -> List[torch.Tensor]:
+                       bits: int, apply=None) -> List[torch.Tensor]:
     """simple_aggregate over K payloads of the entries `names` (every client's entry decodable by
     _decode_stoch, one shape): both byte planes of every client staged as device rows, one launch of
-    adfl_stoch_dequantize_mean_batched, one owned fp32 tensor per entry (CPU when the payloads are)."""
+    adfl_stoch_dequantize_mean_batched, one owned fp32 tensor per entry (CPU when the payloads are). apply =
+    (bases, where, alpha, beta): the fused decode-mean + axpby over the same rows instead (_mean_axpby_out), one
+    owned tensor per entry where its base lives."""
     st = _staging()
     dev = st.device
     first = all_c_params[0].params
@@ -780,6 +782,11 @@ def _decode_mean_stoch(all_c_params: List[QuantParameters], names: List[str], co
                          dtype=torch.float32).to(dev, non_blocking=True)
     mins = (torch.tensor([[float(c.params[n].scale_2) for n in names] for c in all_c_params],
                          dtype=torch.float32).to(dev, non_blocking=True) if codec == "rqsgd" else None)
+    if apply is not None:
+        bases, where, alpha, beta = apply
+        return _mean_axpby_out(st, lay, [first[n].data.shape for n in names], bases, where, "sm_out",
+                               lambda b, o: sops.dequantize_mean_axpby_batched(codec, lv_rows, sg_rows, norms, mins,
+                                                                               lay, bits, b, o, alpha, beta))
     out_dev = sops.dequantize_mean_batched(codec, lv_rows, sg_rows, norms, lay, bits, mins=mins,
                                            out=st.buf("sm_out", lay.total, torch.float32))
     on_cpu = [not any(c.params[n].data.is_cuda for c in all_c_params) for n in names]
@@ -789,7 +796,7 @@ def _decode_mean_stoch(all_c_params: List[QuantParameters], names: List[str], co
 @_serialized
 def _decode_mean_stoch_host(like: List[torch.Tensor], numel: torch.Tensor, lv_ptrs: List[np.ndarray],
                             sg_ptrs: List[np.ndarray], norms: torch.Tensor, mins, codec: str,
-                            bits: int) -> List[torch.Tensor]:
+                            bits: int, apply=None) -> List[torch.Tensor]:
     """_decode_mean_stoch for K CPU updates already checked (_StochChannel._mean_host_updates): both planes of
     every client gathered straight from the storages into pinned rows (_rows_from_ptrs, once per plane), one
     decode-mean launch, the fp32 means handed back as owned CPU tensors shaped like `like`, created by one
@@ -802,6 +809,11 @@ def _decode_mean_stoch_host(like: List[torch.Tensor], numel: torch.Tensor, lv_pt
     sg_rows = _rows_from_ptrs(sg_ptrs, lay, st, "sm_signs").view(torch.int8)
     nd = norms.to(dev, non_blocking=True)
     md = mins.to(dev, non_blocking=True) if mins is not None else None
+    if apply is not None:   # as _decode_mean_stoch's
+        bases, where, alpha, beta = apply
+        return _mean_axpby_out(st, lay, [t.shape for t in like], bases, where, "sm_out",
+                               lambda b, o: sops.dequantize_mean_axpby_batched(codec, lv_rows, sg_rows, nd, md, lay,
+                                                                               bits, b, o, alpha, beta), like=like)
     out_dev = sops.dequantize_mean_batched(codec, lv_rows, sg_rows, nd, lay, bits, mins=md,
                                            out=st.buf("sm_out", lay.total, torch.float32))
     return _hand_out(out_dev, lay, [None] * len(like), [True] * len(like), st, "sm_out", like=like)
@@ -886,6 +898,17 @@ class _StochChannel(_CodecChannel):
         element count and, across updates, one shape. Returns (those names, their means, no passthrough names:
         the other entries all go through _receive), or None when the updates are anything else (receive_mean
         then classifies entry by entry)."""
+        cls = self._mean_host_classify(all_c_params, names)
+        if cls is None:
+            return None
+        if not cls[0]:
+            return [], [], []
+        return cls[0], _decode_mean_stoch_host(*cls[1:], self.CODEC, self.bits), []
+
+    def _mean_host_classify(self, all_c_params: List[QuantParameters], names: List[str]):
+        """_mean_host_updates' classification: (those names, then _decode_mean_stoch_host's staging arguments:
+        the first update's level planes, the element counts, every update's level and sign pointers, the [K, T]
+        norms and RQSGD's minima), or None."""
         if any(list(c.params.keys()) != names for c in all_c_params):
             return None
         th = _torchhost.get()
@@ -897,7 +920,7 @@ class _StochChannel(_CodecChannel):
             return None
         idx = np.nonzero((ndim > 1) & (numel > 0))[0].tolist()
         if not idx:
-            return [], [], []
+            return [], [], None, [], [], None, None
         lv = [[d[i] for i in idx] for d in datas]
         sg = [[c[i].signs for i in idx] for c in ps]
         lvm = [th.byte_planes(x) for x in lv]
@@ -910,10 +933,15 @@ class _StochChannel(_CodecChannel):
         norms = torch.tensor([[float(c[i].scale) for i in idx] for c in ps], dtype=torch.float32)
         mins = (torch.tensor([[float(c[i].scale_2) for i in idx] for c in ps], dtype=torch.float32)
                 if self.CODEC == "rqsgd" else None)
-        means = _decode_mean_stoch_host(lv[0], n0, [m[2].numpy().view(np.uint64) for m in lvm],
-                                        [m[2].numpy().view(np.uint64) for m in sgm], norms, mins, self.CODEC,
-                                        self.bits)
-        return [names[i] for i in idx], means, []
+        return ([names[i] for i in idx], lv[0], n0, [m[2].numpy().view(np.uint64) for m in lvm],
+                [m[2].numpy().view(np.uint64) for m in sgm], norms, mins)
+
+    def _mean_apply(self, all_c_params: List[QuantParameters], names: List[str], bases: List[torch.Tensor],
+                    where: str, alpha: float, beta: float, host) -> List[torch.Tensor]:
+        apply = (bases, where, alpha, beta)
+        if host is not None:   # K CPU updates, classified natively: rows staged straight from the storages
+            return _decode_mean_stoch_host(*host[1:], self.CODEC, self.bits, apply=apply)
+        return _decode_mean_stoch(all_c_params, names, self.CODEC, self.bits, apply=apply)
 
     @staticmethod
     def _fusable(p: QuantParameter) -> bool:

@@ -74,6 +74,10 @@ SIGNATURES = {
     "adfl_stoch_dequantize_axpby_batched": (INT, [I32, P, P, P, I64, INT, P, P, P, P, I32, I32, F32, F32, P]),
     "adfl_slq_dequantize_mean_batched": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
     "adfl_slq_dequantize_mean_batched_int4": (INT, [P, I64, I32, P, I64, P, I64, I32, P, P, P]),
+    "adfl_slq_dequantize_mean_axpby_batched": (INT, [P, I64, I32, P, I64, P, I64, P, P, I32, F32, F32, P]),
+    "adfl_slq_dequantize_mean_axpby_batched_int4": (INT, [P, I64, I32, P, I64, P, I64, P, P, I32, F32, F32, P]),
+    "adfl_stoch_dequantize_mean_axpby_batched": (INT, [I32, P, P, I64, I32, P, I64, INT, P, P, I64, P, P, I32, F32,
+                                                       F32, P]),
     "adfl_slq_encode_delta_batched": (INT, [P, P, P, I64, INT, P, P, P, P]),
     "adfl_slq_encode_delta_batched_work": (INT, [P, P, P, I64, P, I64, INT, P, P, P, P]),
     "adfl_slq_encode_delta_batched_int4": (INT, [P, P, P, I64, INT, P, P, P, P]),

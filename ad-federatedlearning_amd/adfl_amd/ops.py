@@ -580,6 +580,47 @@ def dequantize_mean_batched(q_rows: torch.Tensor, scales: torch.Tensor, layout: 
     return out
 
 
+def mean_axpby_tables(bases, outs, layout: BucketLayout, dev: torch.device):
+    """(device table of base pointers, device table of output pointers) for the fused decode-mean + axpby entries:
+    each side one flat fp32 bucket in `layout` or a sequence of T tensors, checked as apply_tables checks one
+    target."""
+    if bases is None:
+        raise ValueError("dequantize_mean_axpby_batched: bases is required")
+    one = lambda side: side if isinstance(side, torch.Tensor) else [list(side)]   # noqa: E731
+    b_tab, o_tab, _ = apply_tables(one(bases), one(outs), layout, dev)
+    return b_tab, o_tab
+
+
+def dequantize_mean_axpby_batched(q_rows: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, bases, outs,
+                                  alpha: float, beta: float, packed: bool = False) -> None:
+    """Fused decode-mean + axpby, the synchronous DELTA server step (adfl_slq_dequantize_mean_axpby_batched):
+    Simple(CommType.DELTA, sync=True)._sync_update's add_parameters(g, simple_aggregate(decoded), alpha, beta)
+    (Src/ADFL/Strategy/simple.py:87-89) in one launch. For every tensor t, with m what dequantize_mean_batched
+    writes for the same rows (torch-order sum of the K decodes, then / K),
+        outs[t] = fp32(fp32(alpha * bases[t]) + fp32(beta * m))
+    three separately rounded fp32 operations. q_rows / scales as dequantize_mean_batched takes them; bases / outs:
+    each one flat fp32 device bucket in `layout`, or T contiguous, 16-byte aligned fp32 device tensors with
+    layout.sizes[t] elements; outs[t] may be bases[t] itself (in place). packed=True: int4-packed rows."""
+    dt = torch.uint8 if packed else torch.int8
+    if q_rows.dim() != 2 or q_rows.dtype != dt or not q_rows.is_contiguous() or not q_rows.is_cuda:
+        raise ValueError(f"dequantize_mean_axpby_batched: q_rows must be a contiguous [K, row_bytes] {dt} device "
+                         "tensor")
+    k, row = q_rows.shape
+    if packed:
+        _require_even_offsets(layout)
+    if row < ((layout.total + 1) // 2 if packed else layout.total):
+        raise ValueError("dequantize_mean_axpby_batched: rows shorter than the bucket layout")
+    dev = q_rows.device
+    sc = _scale_rows(scales, k, layout.ntensors, dev, "scales")
+    b_tab, o_tab = mean_axpby_tables(bases, outs, layout, dev)
+    lib = _lib.load()
+    fn = lib.adfl_slq_dequantize_mean_axpby_batched_int4 if packed else lib.adfl_slq_dequantize_mean_axpby_batched
+    check(fn(q_rows.data_ptr(), row, k, layout.device_chunks(dev).data_ptr(), layout.nchunks, sc.data_ptr(),
+             sc.stride(0), b_tab.data_ptr(), o_tab.data_ptr(), layout.ntensors, float(alpha), float(beta),
+             _stream(dev)))
+    # the tables may be freed on return: the caching allocator only reuses them for later work on this stream
+
+
 def _require_even_offsets(layout: BucketLayout) -> None:
     if layout.align % 2 or (layout.offsets % 2).any():
         raise ValueError("int4 buckets need even tensor offsets (BucketLayout(align=2) or a multiple of 2)")
@@ -1093,6 +1134,47 @@ def slq_decode_axpby_batched_int4_op(packed: torch.Tensor, scales: torch.Tensor,
 
 @slq_decode_axpby_batched_int4_op.register_fake
 def _(packed, scales, base, offsets, sizes, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
+def _decode_mean_axpby_flat(q_rows: torch.Tensor, scales: torch.Tensor, base: torch.Tensor, lay: BucketLayout,
+                            alpha: float, beta: float, packed: bool) -> torch.Tensor:
+    """slq_decode_mean_axpby_batched's body: a new fp32 bucket shaped like `base`."""
+    base = base.reshape(-1)
+    if base.dtype != torch.float32:
+        raise ValueError(f"slq_decode_mean_axpby_batched: the base bucket must be float32, got {base.dtype}")
+    if base.numel() < lay.total:
+        raise ValueError("slq_decode_mean_axpby_batched: base bucket smaller than the layout")
+    out = _filled(base.numel(), torch.float32, base.device, lay)
+    dequantize_mean_axpby_batched(q_rows, scales, lay, _dev(base, "base"), out, alpha, beta, packed=packed)
+    return out
+
+
+# The synchronous DELTA server step (Strategy/simple.py:87-89), beside the other server steps.
+@torch.library.custom_op("adfl_apply::slq_decode_mean_axpby_batched", mutates_args=())
+def slq_decode_mean_axpby_batched_op(q_rows: torch.Tensor, scales: torch.Tensor, base: torch.Tensor,
+                                     offsets: torch.Tensor, sizes: torch.Tensor, alpha: float,
+                                     beta: float) -> torch.Tensor:
+    """fp32(fp32(alpha * base) + fp32(beta * mean of the K decodes)) per tensor of a caller-placed layout (q_rows
+    [K, row_bytes] int8, scales [K, T]), as a new bucket shaped like `base`; positions no tensor owns are zero."""
+    return _decode_mean_axpby_flat(q_rows, scales, base, layout_for(offsets, sizes), alpha, beta, False)
+
+
+@slq_decode_mean_axpby_batched_op.register_fake
+def _(q_rows, scales, base, offsets, sizes, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_decode_mean_axpby_batched_int4", mutates_args=())
+def slq_decode_mean_axpby_batched_int4_op(packed_rows: torch.Tensor, scales: torch.Tensor, base: torch.Tensor,
+                                          offsets: torch.Tensor, sizes: torch.Tensor, alpha: float,
+                                          beta: float) -> torch.Tensor:
+    """slq_decode_mean_axpby_batched over int4-packed rows (uint8 [K, row_bytes], even tensor offsets)."""
+    return _decode_mean_axpby_flat(packed_rows, scales, base, layout_for(offsets, sizes), alpha, beta, True)
+
+
+@slq_decode_mean_axpby_batched_int4_op.register_fake
+def _(packed_rows, scales, base, offsets, sizes, alpha, beta):
     return base.new_empty((base.numel(),), dtype=torch.float32)
 
 

@@ -752,6 +752,66 @@ def dequantize_axpby_batched(codec: str, levels: torch.Tensor, signs: torch.Tens
         float(beta), _stream(dev)))
 
 
+def dequantize_mean_axpby_batched(codec: str, levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                  mins: Optional[torch.Tensor], layout: BucketLayout, bits: int, bases, outs,
+                                  alpha: float, beta: float) -> None:
+    """ops.dequantize_mean_axpby_batched for the stochastic codecs (adfl_stoch_dequantize_mean_axpby_batched): the
+    synchronous DELTA server step, add_parameters(g, simple_aggregate(K decodes), alpha, beta)
+    (Src/ADFL/Strategy/simple.py:87-89) in one launch. With m what dequantize_mean_batched writes for the same
+    planes, outs[t] = fp32(fp32(alpha * bases[t]) + fp32(beta * m)). levels / signs: [K, row] byte planes, norms
+    (RQSGD: mins, else None) [K, ntensors] fp32; bases / outs as ops.dequantize_mean_axpby_batched takes them."""
+    from .ops import mean_axpby_tables
+    _check_codec(codec)
+    levels, signs, norms = _dev(levels, "levels"), _dev(signs, "signs"), _dev(norms, "norms")
+    if levels.dim() != 2 or signs.shape != levels.shape or levels.element_size() != 1 or signs.element_size() != 1:
+        raise ValueError("adfl_amd.stoch: levels / signs must be [K, row] byte planes of one shape")
+    k, row = levels.shape
+    if row < layout.total or not levels.is_contiguous() or not signs.is_contiguous():
+        raise ValueError(f"adfl_amd.stoch: rows of {row} bytes cannot hold the {layout.total}-element bucket")
+    if norms.shape != (k, layout.ntensors) or norms.dtype != torch.float32 or not norms.is_contiguous():
+        raise ValueError(f"adfl_amd.stoch: norms must be contiguous fp32 [{k}, {layout.ntensors}]")
+    if codec == "rqsgd":
+        if mins is None:
+            raise ValueError("adfl_amd.stoch: RQSGD needs mins")
+        mins = _dev(mins, "mins")
+        if mins.shape != norms.shape or mins.dtype != torch.float32 or not mins.is_contiguous():
+            raise ValueError("adfl_amd.stoch: mins must match norms")
+    else:
+        mins = None
+    dev = levels.device
+    b_tab, o_tab = mean_axpby_tables(bases, outs, layout, dev)
+    check(_lib.load().adfl_stoch_dequantize_mean_axpby_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signs.data_ptr(), row, k, layout.device_chunks(dev).data_ptr(),
+        layout.nchunks, bits, norms.data_ptr(), mins.data_ptr() if mins is not None else None, layout.ntensors,
+        b_tab.data_ptr(), o_tab.data_ptr(), layout.ntensors, float(alpha), float(beta), _stream(dev)))
+
+
+@torch.library.custom_op("adfl_apply::stoch_decode_mean_axpby_batched", mutates_args=())
+def stoch_decode_mean_axpby_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                       mins: torch.Tensor, base: torch.Tensor, offsets: torch.Tensor,
+                                       sizes: torch.Tensor, codec: str, bits: int, alpha: float,
+                                       beta: float) -> torch.Tensor:
+    """fp32(fp32(alpha * base) + fp32(beta * mean of the K decodes)) per tensor of K rows of stoch_encode_batched's
+    planes ([K, row]; norms / mins [K, T], mins used by RQSGD only), as a new bucket shaped like `base`
+    (positions no tensor owns are zero)."""
+    from .ops import _filled, layout_for
+    _check_codec(codec)
+    lay = layout_for(offsets, sizes)
+    base = base.reshape(-1)
+    if base.dtype != torch.float32 or base.numel() < lay.total:
+        raise ValueError("stoch_decode_mean_axpby_batched: base must be an fp32 bucket of at least the layout's "
+                         "extent")
+    out = _filled(base.numel(), torch.float32, base.device, lay)
+    dequantize_mean_axpby_batched(codec, levels.view(torch.uint8), signs, norms, mins if codec == "rqsgd" else None,
+                                  lay, bits, _dev(base, "base"), out, alpha, beta)
+    return out
+
+
+@stoch_decode_mean_axpby_batched_op.register_fake
+def _(levels, signs, norms, mins, base, offsets, sizes, codec, bits, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
 @torch.library.custom_op("adfl_apply::stoch_decode_axpby_batched", mutates_args=())
 def stoch_decode_axpby_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor, mins: torch.Tensor,
                                   base: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str,

@@ -101,6 +101,56 @@ __device__ __forceinline__ void apply_chunk(const float4 (&dv)[kApplyGroups], bo
   }
 }
 
+// The tail of the fused decode-mean + axpby kernels (the synchronous DELTA server step, Strategy/simple.py:87-89):
+// one chunk's slice of its tensor's base g and output o (a.base / a.out: one pointer per tensor, ntargets == 1).
+// m, the mean of element i of the chunk, becomes fp32(fp32(af * g[i]) + fp32(bf * m)). vec (block-uniform): the
+// float4 groups from chunk element `head` on are 16-byte aligned in both g and o.
+struct MeanAxpbyOut {
+  const float* g;  // the chunk's slice of its tensor's base: element i of the chunk at g[i]
+  float* o;        // likewise the output
+  float af, bf;
+  bool inplace;
+  bool vec;        // tiles from chunk element `head` on: 16-byte accesses
+
+  __device__ __forceinline__ MeanAxpbyOut(const ApplyTargets& a, const adfl_slq_chunk& c, int64_t in_tensor, int head)
+      : g(a.base[c.tensor] + in_tensor), o(a.out[c.tensor] + in_tensor), af(a.af), bf(a.bf) {
+    inplace = (g == o);
+    vec = (((reinterpret_cast<uintptr_t>(g + head) | reinterpret_cast<uintptr_t>(o + head)) & 15u) == 0);
+  }
+  __device__ __forceinline__ void store1(int i, float m) const {
+    const float v = apply1(g, i, m, af, bf);
+    if (inplace) {
+      o[i] = v;
+    } else {
+      __builtin_nontemporal_store(v, o + i);
+    }
+  }
+  // the float4 of g at chunk element i (vec: 16-byte aligned)
+  __device__ __forceinline__ float4 load4g(int i) const {
+    if (vec) return *reinterpret_cast<const float4*>(g + i);
+    return make_float4(g[i], g[i + 1], g[i + 2], g[i + 3]);
+  }
+  __device__ __forceinline__ void store4(int i, float4 gv, float4 m) const {
+    const float4 r = apply4(gv, m, af, bf, true);
+    if (vec) {
+      if (inplace) {
+        *reinterpret_cast<float4*>(o + i) = r;
+      } else {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v v = {r.x, r.y, r.z, r.w};
+        __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(o + i));
+      }
+    } else if (inplace) {
+      o[i] = r.x, o[i + 1] = r.y, o[i + 2] = r.z, o[i + 3] = r.w;
+    } else {
+      __builtin_nontemporal_store(r.x, o + i);
+      __builtin_nontemporal_store(r.y, o + i + 1);
+      __builtin_nontemporal_store(r.z, o + i + 2);
+      __builtin_nontemporal_store(r.w, o + i + 3);
+    }
+  }
+};
+
 // Host-side argument check shared by the three entry points (nothing is launched when it fails).
 inline bool apply_bad_args(const void* d_chunks, int64_t nchunks, const void* d_out, int32_t ntensors,
                            int32_t ntargets) {

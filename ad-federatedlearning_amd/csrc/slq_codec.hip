@@ -701,6 +701,109 @@ __global__ __launch_bounds__(kBlock) void k_dequantize_mean_batched_int4(
   }
 }
 
+// Synchronous DELTA server step: Simple(CommType.DELTA, sync=True)._sync_update (Strategy/simple.py:87-89),
+// add_parameters(g, simple_aggregate(K decodes), alpha, beta) in one launch. The mean kernels above with another
+// tail (MeanAxpbyOut, apply_device.h): m is the value k_dequantize_mean_batched[_int4] writes (no self row), and
+//   out = fp32(fp32(alpha * g) + fp32(beta * m))          apply_device.h's AXPBY, never an FMA
+// with g and out addressed as server_flush.hip addresses its operands: one fp32 pointer per tensor (a.base /
+// a.out, ntargets == 1), so separate tensors and bucket + offset[t] are one form. A tensor's slot in the payload
+// bucket and its g / out tensor generally differ in phase: when the chunk's tile slices of g and out are both
+// 16-byte aligned (every tile of a chunk starts a multiple of 1024 elements after the first, so the choice is
+// block-uniform) they take 16-byte accesses, otherwise 4-byte accesses of the same elements. A tile's g is loaded
+// before its row loop, so its latency hides under the K payload rows. Out of place the output takes the decode's
+// non-temporal stores; in place (out == g: the thread that writes an element is the one that read it) plain ones.
+template <bool DEEP>
+__global__ __launch_bounds__(kBlock) void k_dequantize_mean_axpby_batched(const int8_t* __restrict__ q,
+                                                                          int64_t row_stride, int k,
+                                                                          const adfl_slq_chunk* __restrict__ chunks,
+                                                                          const float* __restrict__ scales,
+                                                                          int64_t scale_stride, ApplyTargets a) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kWaves][kTile / 4];
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const TensorSpan ts = tensor_span(chunks, c);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double dk = (double)k;
+  const int head = chunk_head(c.start, c.len, 16);
+  const int ntiles = seq_tiles(c, ts, head, kTile);
+  const MeanAxpbyOut w(a, c, c.start - ts.start, head);
+  auto dq = [&](int r, int64_t e) -> float {
+    return scales[r * scale_stride + c.tensor] * (float)q[r * row_stride + e];
+  };
+  auto one = [&](int i) {
+    const int64_t e = c.start + i;
+    w.store1(i, mean_elem_torch(dq, k, -1, nullptr, e, e - ts.start, ts.n, dk));
+  };
+  if ((int)threadIdx.x < head) one(threadIdx.x);
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int off = head + t * kTile;           // chunk-relative
+    const int64_t base = c.start + off;         // 16-element aligned in the payload bucket
+    float4 gv[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gv[j] = w.load4g(off + 4 * (j * 64 + lane));
+    adfl_sum::SeqTile<4, DEEP> acc;
+    acc.init();
+    for (int r = 0; r < k; ++r) {
+      const uint4* q16 = reinterpret_cast<const uint4*>(q + r * row_stride + base);
+      const float s = scales[r * scale_stride + c.tensor];
+      reinterpret_cast<uint4*>(lds[wave])[lane] = q16[lane];
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc.add(j, dequant4(lds[wave][j * 64 + lane], s));
+      __builtin_amdgcn_wave_barrier();
+      acc.step();
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w.store4(off + 4 * (j * 64 + lane), gv[j], div4(acc.result(j), dk));
+  }
+  for (int i = head + ntiles * kTile + threadIdx.x; i < c.len; i += kBlock) one(i);
+}
+
+template <bool DEEP>
+__global__ __launch_bounds__(kBlock) void k_dequantize_mean_axpby_batched_int4(
+    const uint8_t* __restrict__ p, int64_t row_stride, int k, const adfl_slq_chunk* __restrict__ chunks,
+    const float* __restrict__ scales, int64_t scale_stride, ApplyTargets a) {
+  __shared__ __attribute__((aligned(16))) uint16_t lds[kWaves][kTile4 / 4];
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const TensorSpan ts = tensor_span(chunks, c);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double dk = (double)k;
+  const int head = chunk_head(c.start, c.len, 32);
+  const int ntiles = seq_tiles(c, ts, head, kTile4);
+  const MeanAxpbyOut w(a, c, c.start - ts.start, head);
+  auto dq = [&](int r, int64_t e) -> float {
+    float e0, e1;
+    dequant_byte_int4(p[r * row_stride + (e >> 1)], scales[r * scale_stride + c.tensor], e0, e1);
+    return (e & 1) ? e1 : e0;
+  };
+  auto one = [&](int i) {
+    const int64_t e = c.start + i;
+    w.store1(i, mean_elem_torch(dq, k, -1, nullptr, e, e - ts.start, ts.n, dk));
+  };
+  if ((int)threadIdx.x < head) one(threadIdx.x);
+  for (int t = wave; t < ntiles; t += kWaves) {
+    const int off = head + t * kTile4;          // chunk-relative
+    const int64_t base = c.start + off;         // 32-element aligned in the payload bucket
+    float4 gv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) gv[j] = w.load4g(off + 4 * (j * 64 + lane));
+    adfl_sum::SeqTile<8, DEEP> acc;
+    acc.init();
+    for (int r = 0; r < k; ++r) {
+      const uint4* p16 = reinterpret_cast<const uint4*>(p + r * row_stride + (base >> 1));
+      const float s = scales[r * scale_stride + c.tensor];
+      reinterpret_cast<uint4*>(lds[wave])[lane] = p16[lane];
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc.add(j, dequant2_int4(lds[wave][j * 64 + lane], s));
+      __builtin_amdgcn_wave_barrier();
+      acc.step();
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w.store4(off + 4 * (j * 64 + lane), gv[j], div4(acc.result(j), dk));
+  }
+  for (int i = head + ntiles * kTile4 + threadIdx.x; i < c.len; i += kBlock) one(i);
+}
+
 // Decode + accumulate into K models (pool.py:62-75, qafel.py:176-179 via model.py:337-347): the chunk's
 // payload is decoded once into registers (8 float4 per thread), then every model's slice is read, added
 // (fp32(a + d), what mul_(1).add_(d, alpha=1) computes) and written back with 16-byte accesses when the
@@ -1227,6 +1330,38 @@ int adfl_slq_dequantize_mean_batched_int4(const uint8_t* d_packed, int64_t row_s
   auto kern = k >= kDeepRows ? k_dequantize_mean_batched_int4<true> : k_dequantize_mean_batched_int4<false>;
   hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_packed, row_stride_bytes,
                      (int)k, d_chunks, d_scales, scale_stride, (int)self_row, d_self_x, d_out);
+  return launch_status();
+}
+
+int adfl_slq_dequantize_mean_axpby_batched(const int8_t* d_q, int64_t row_stride_bytes, int32_t k,
+                                           const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_scales,
+                                           int64_t scale_stride, const float* const* d_base, float* const* d_out,
+                                           int32_t ntensors, float alpha, float beta, void* stream) {
+  if (!d_q || !d_scales || !d_base || apply_bad_args(d_chunks, nchunks, d_out, ntensors, 1) || bad_rows(k) ||
+      scale_stride < 1 || row_stride_bytes < 1 || (row_stride_bytes & 15) != 0)
+    return ADFL_E_ARG;
+  if (!aligned16(d_q)) return ADFL_E_ALIGN;
+  const ApplyTargets a{d_base, d_out, (int)ntensors, 1, alpha, beta};
+  auto kern = k >= kDeepRows ? k_dequantize_mean_axpby_batched<true> : k_dequantize_mean_axpby_batched<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_q, row_stride_bytes,
+                     (int)k, d_chunks, d_scales, scale_stride, a);
+  return launch_status();
+}
+
+int adfl_slq_dequantize_mean_axpby_batched_int4(const uint8_t* d_packed, int64_t row_stride_bytes, int32_t k,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                                const float* d_scales, int64_t scale_stride,
+                                                const float* const* d_base, float* const* d_out, int32_t ntensors,
+                                                float alpha, float beta, void* stream) {
+  if (!d_packed || !d_scales || !d_base || apply_bad_args(d_chunks, nchunks, d_out, ntensors, 1) || bad_rows(k) ||
+      scale_stride < 1 || row_stride_bytes < 1 || (row_stride_bytes & 15) != 0)
+    return ADFL_E_ARG;
+  if (!aligned16(d_packed)) return ADFL_E_ALIGN;
+  const ApplyTargets a{d_base, d_out, (int)ntensors, 1, alpha, beta};
+  auto kern =
+      k >= kDeepRows ? k_dequantize_mean_axpby_batched_int4<true> : k_dequantize_mean_axpby_batched_int4<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_packed, row_stride_bytes,
+                     (int)k, d_chunks, d_scales, scale_stride, a);
   return launch_status();
 }
 

@@ -944,6 +944,81 @@ __global__ __launch_bounds__(kBlock) void k_stoch_dequantize_mean(const uint8_t*
   }
 }
 
+// The synchronous DELTA server step (Strategy/simple.py:87-89): k_stoch_dequantize_mean with apply_device.h's
+// MeanAxpbyOut tail — m as above, out = fp32(fp32(alpha * g) + fp32(beta * m)) through one pointer per tensor for
+// g and out. A thread's g groups are loaded before the row loop (their latency hides under the K rows): 16-byte
+// accesses when the chunk's groups are 16-byte aligned in both g and out (block-uniform), else 4-byte ones.
+template <int KIND, bool DEEP>
+__global__ __launch_bounds__(kBlock) void k_stoch_dequantize_mean_axpby(const uint8_t* __restrict__ levels,
+                                                                        const uint8_t* __restrict__ signs,
+                                                                        int64_t row_stride, int k,
+                                                                        const adfl_slq_chunk* __restrict__ chunks,
+                                                                        const float* __restrict__ norms,
+                                                                        const float* __restrict__ mins,
+                                                                        int64_t norm_stride, float s, ApplyTargets a) {
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const int64_t t_start = chunks[c.first_chunk].start;
+  const int64_t t_n = (int64_t)(c.nchunks - 1) * ADFL_SLQ_CHUNK_ELEMS + chunks[c.first_chunk + c.nchunks - 1].len;
+  const int head = chunk_head4(c.start, c.len);
+  int64_t lim = t_start + adfl_sum::seq_end(t_n) - c.start;  // chunk-relative end of the SEQ columns
+  lim = lim < c.len ? lim : c.len;
+  const int n4 = lim > head ? (int)((lim - head) >> 2) : 0;  // dword groups wholly in SEQ columns
+  const double dk = (double)k;
+  const MeanAxpbyOut w(a, c, c.start - t_start, head);
+  float4 gv[kPer];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int q = threadIdx.x + j * kBlock;
+    gv[j] = q < n4 ? w.load4g(head + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  adfl_sum::SeqTile<kPer, DEEP> acc;
+  acc.init();
+  for (int r = 0; r < k; ++r) {
+    const float norm = norms[r * norm_stride + c.tensor];
+    const float mn = KIND == 1 ? mins[r * norm_stride + c.tensor] : 0.0f;
+    const uint32_t* l4 = reinterpret_cast<const uint32_t*>(levels + r * row_stride + c.start + head);
+    const uint32_t* g4 = reinterpret_cast<const uint32_t*>(signs + r * row_stride + c.start + head);
+    uint32_t L[kPer], G[kPer];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      const int q = threadIdx.x + j * kBlock;
+      L[j] = q < n4 ? l4[q] : 0u;
+      G[j] = q < n4 ? g4[q] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+      if ((int)threadIdx.x + j * kBlock < n4)
+        acc.add(j, make_float4(mean_term<KIND>(L[j] & 0xffu, G[j] & 0xffu, norm, mn, s),
+                               mean_term<KIND>((L[j] >> 8) & 0xffu, (G[j] >> 8) & 0xffu, norm, mn, s),
+                               mean_term<KIND>((L[j] >> 16) & 0xffu, (G[j] >> 16) & 0xffu, norm, mn, s),
+                               mean_term<KIND>(L[j] >> 24, G[j] >> 24, norm, mn, s)));
+    }
+    acc.step();
+  }
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int q = threadIdx.x + j * kBlock;
+    if (q < n4) {
+      const float4 m = acc.result(j);
+      w.store4(head + 4 * q, gv[j],
+               make_float4((float)((double)m.x / dk), (float)((double)m.y / dk), (float)((double)m.z / dk),
+                           (float)((double)m.w / dk)));
+    }
+  }
+  // head elements and those past the SEQ groups: each in its own order
+  const int rest = c.len - (head + (n4 << 2));
+  for (int t = threadIdx.x; t < head + rest; t += kBlock) {
+    const int i = t < head ? t : head + (n4 << 2) + (t - head);
+    auto get = [&](int r) -> float {
+      const float norm = norms[r * norm_stride + c.tensor];
+      const float mn = KIND == 1 ? mins[r * norm_stride + c.tensor] : 0.0f;
+      return mean_term<KIND>(levels[r * row_stride + c.start + i], signs[r * row_stride + c.start + i], norm, mn, s);
+    };
+    const int64_t j = c.start + i - t_start;
+    w.store1(i, (float)((double)adfl_sum::sum_elem(get, k, adfl_sum::mode_of(j, t_n, k)) / dk));
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_philox_uniforms(float* __restrict__ out, int64_t n, int64_t start,
                                                             Uniforms U) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
@@ -1213,6 +1288,34 @@ int adfl_stoch_dequantize_mean_batched(int32_t codec, const uint8_t* d_levels, c
                                               : (deep ? k_stoch_dequantize_mean<2, true> : k_stoch_dequantize_mean<2, false>);
   hipLaunchKernelGGL(kern, grid, block, 0, st, d_levels, sg, row_stride_bytes, k, d_chunks, d_norms, d_mins, norm_stride,
                      s, d_out);
+  return launch_status();
+}
+
+int adfl_stoch_dequantize_mean_axpby_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                             int64_t row_stride_bytes, int32_t k, const adfl_slq_chunk* d_chunks,
+                                             int64_t nchunks, int bits, const float* d_norms, const float* d_mins,
+                                             int64_t norm_stride, const float* const* d_base, float* const* d_out,
+                                             int32_t ntensors, float alpha, float beta, void* stream) {
+  if (codec != ADFL_CODEC_QSGD && codec != ADFL_CODEC_RQSGD && codec != ADFL_CODEC_CNAT) return ADFL_E_ARG;
+  if (!d_levels || !d_signs || !d_norms || !d_base || (codec == ADFL_CODEC_RQSGD && !d_mins) ||
+      apply_bad_args(d_chunks, nchunks, d_out, ntensors, 1) || k < 1 || k > adfl_sum::kMaxRows ||
+      row_stride_bytes < 0 || norm_stride < 0 || (k > 1 && (row_stride_bytes == 0 || norm_stride == 0)) ||
+      (row_stride_bytes & 15))
+    return ADFL_E_ARG;
+  if (codec != ADFL_CODEC_CNAT)
+    if (int s = check_bits(bits)) return s;
+  if (!aligned16(d_levels) || !aligned16(d_signs)) return ADFL_E_ALIGN;
+  const float s = codec == ADFL_CODEC_CNAT ? 1.0f : levels_f(bits);
+  const ApplyTargets a{d_base, d_out, (int)ntensors, 1, alpha, beta};
+  const bool deep = k >= 256;
+  auto kern = codec == ADFL_CODEC_QSGD
+                  ? (deep ? k_stoch_dequantize_mean_axpby<0, true> : k_stoch_dequantize_mean_axpby<0, false>)
+                  : codec == ADFL_CODEC_RQSGD
+                        ? (deep ? k_stoch_dequantize_mean_axpby<1, true> : k_stoch_dequantize_mean_axpby<1, false>)
+                        : (deep ? k_stoch_dequantize_mean_axpby<2, true> : k_stoch_dequantize_mean_axpby<2, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_levels,
+                     reinterpret_cast<const uint8_t*>(d_signs), row_stride_bytes, k, d_chunks, d_norms, d_mins,
+                     norm_stride, s, a);
   return launch_status();
 }
 

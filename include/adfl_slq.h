@@ -261,6 +261,33 @@ int adfl_slq_dequantize_axpby_batched_int4(const uint8_t* d_packed, const adfl_s
                                            int32_t ntensors, int32_t ntargets, float alpha, float beta,
                                            void* stream);
 
+/* Fused decode-mean + axpby: the synchronous DELTA server step, Simple(CommType.DELTA, sync=True)._sync_update
+ * (Src/ADFL/Strategy/simple.py:87-89): add_parameters(g, simple_aggregate(K decoded updates), alpha, beta) in one
+ * launch. For tensor t and element i, with m the value adfl_slq_dequantize_mean_batched writes for the same rows
+ * (self_row == -1: the torch-order sum of the K decodes from +0, then / k correctly rounded),
+ *   out[t][i] = fp32(fp32(alpha * base[t][i]) + fp32(beta * m))
+ * three separately rounded fp32 operations, never an FMA (add_parameters, Src/ADFL/model.py:326-334). The K
+ * payloads and the base are read once and the output written once; no mean is materialised.
+ *   d_q, row_stride_bytes, k, d_chunks, d_scales, scale_stride   as adfl_slq_dequantize_mean_batched
+ *   d_base, d_out  DEVICE arrays of ntensors device pointers: tensor t's fp32 storage (contiguous, sizes as the
+ *                  table). Two flat buckets are bucket + offset[t]. d_out[t] == d_base[t] updates in place; any
+ *                  other overlap is undefined. Slices that are 16-byte aligned where the payload's wave tiles
+ *                  fall take 16-byte accesses, any other phase 4-byte ones, with the same results.
+ * ADFL_E_ARG and nothing launched for a null pointer or table, nchunks outside [1, INT32_MAX], ntensors < 1,
+ * k < 1 or above 2^19, scale_stride < 1 or a row_stride_bytes that is not a positive multiple of 16;
+ * ADFL_E_ALIGN for a d_q that is not 16-byte aligned. */
+int adfl_slq_dequantize_mean_axpby_batched(const int8_t* d_q, int64_t row_stride_bytes, int32_t k,
+                                           const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_scales,
+                                           int64_t scale_stride, const float* const* d_base, float* const* d_out,
+                                           int32_t ntensors, float alpha, float beta, void* stream);
+/* Same over K int4-packed bucket payloads (adfl_slq_dequantize_mean_batched_int4's rows: every tensor offset in
+ * d_chunks EVEN -- the table lives on the device, so this is the caller's contract; the Python layer checks it). */
+int adfl_slq_dequantize_mean_axpby_batched_int4(const uint8_t* d_packed, int64_t row_stride_bytes, int32_t k,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                                const float* d_scales, int64_t scale_stride,
+                                                const float* const* d_base, float* const* d_out, int32_t ntensors,
+                                                float alpha, float beta, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Delta encode — the send side of a CommType.DELTA round: diff_parameters(prev, new)
  * (Src/ADFL/model.py:350-358: new - prev per tensor) followed by SLQChannel._quantize_params

@@ -140,13 +140,25 @@ int adfl_cnat_dequantize_batched(const int8_t* d_exps, const int8_t* d_signs, co
  * fp32(((0 + d_0[i]) + ... + d_{K-1}[i]) / K), d_r the codec's decode (above) of row r's level / exponent
  * and sign bytes (d_levels / d_signs + r * row_stride_bytes, each a bucket payload over d_chunks) under row
  * r's norms d_norms + r * norm_stride (RQSGD: d_mins likewise; +0 where a norm is 0). codec: ADFL_CODEC_*
- * (bits unused for CNAT). Bases 16-byte aligned, row_stride_bytes a multiple of 16. Bit-identical to torch's
- * CPU sum for K <= 4 (it adds rows in order from zero); from K = 5 torch regroups, within fp32 summation
- * error. */
+ * (bits unused for CNAT). Bases 16-byte aligned, row_stride_bytes a multiple of 16. The sum follows torch's
+ * CPU order for sum(stack(rows), dim=0) (csrc/torch_sum_order.h: per tensor, by the element's index in it), so
+ * the result is bit-identical to simple_aggregate on CPU tensors for every K up to 2^19. */
 int adfl_stoch_dequantize_mean_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
                                        int64_t row_stride_bytes, int32_t k, const adfl_slq_chunk* d_chunks,
                                        int64_t nchunks, int bits, const float* d_norms, const float* d_mins,
                                        int64_t norm_stride, float* d_out, void* stream);
+
+/* Fused decode-mean + axpby for the three stochastic codecs: adfl_slq_dequantize_mean_axpby_batched (adfl_slq.h)
+ * with m the value adfl_stoch_dequantize_mean_batched writes for the same rows -- the synchronous DELTA server
+ * step (Src/ADFL/Strategy/simple.py:87-89): out[t][i] = fp32(fp32(alpha * base[t][i]) + fp32(beta * m)). d_base /
+ * d_out: device arrays of ntensors pointers, d_out[t] == d_base[t] in place. ADFL_E_ARG and nothing launched for
+ * an unknown codec, a null pointer or table, nchunks outside [1, INT32_MAX], ntensors < 1, k < 1 or above 2^19, or
+ * a row_stride_bytes that is not a multiple of 16; ADFL_E_BITS for bits outside [1, 16] (QSGD / RQSGD). */
+int adfl_stoch_dequantize_mean_axpby_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                             int64_t row_stride_bytes, int32_t k, const adfl_slq_chunk* d_chunks,
+                                             int64_t nchunks, int bits, const float* d_norms, const float* d_mins,
+                                             int64_t norm_stride, const float* const* d_base, float* const* d_out,
+                                             int32_t ntensors, float alpha, float beta, void* stream);
 
 /* Fused decode + axpby for the three stochastic codecs: adfl_slq_dequantize_axpby_batched (adfl_slq.h) with d the
  * codec's decode (quant.py:243-252 / :385-398 / :537-545; +0 for a tensor whose norm is 0) — FedAsync's

@@ -1619,6 +1619,174 @@ def mode_broadcast_stoch(args, world, rank, dev):
     return line
 
 
+def _sync_delta_rows(codec, lay, k, dev, gen):
+    """K random bucket payloads of `codec` on the device (bytes drawn directly: the kernels' time does not depend
+    on the values) and the two launches over them: (mean(out), fused(base, out, alpha, beta), bytes per element)."""
+    from adfl_amd import ops, stoch
+    row = (lay.total + 15) // 16 * 16
+    t = lay.ntensors
+    sc = (torch.rand((k, t), device=dev, generator=gen) + 0.5) * 1e-3
+    if codec in ("slq8", "slq4"):
+        packed = codec == "slq4"
+        width = (row // 2 + 15) // 16 * 16 if packed else row
+        q = torch.randint(0, 256, (k, width), device=dev, generator=gen, dtype=torch.uint8)
+        q = q if packed else q.view(torch.int8)
+        return (lambda out: ops.dequantize_mean_batched(q, sc, lay, out=out, packed=packed),
+                lambda base, out, a, b: ops.dequantize_mean_axpby_batched(q, sc, lay, base, out, a, b, packed=packed),
+                0.5 if packed else 1.0)
+    if codec == "cnat":
+        lv = (-torch.randint(0, 21, (k, row), device=dev, generator=gen, dtype=torch.int8)).view(torch.uint8)
+    else:
+        lv = torch.randint(0, 256, (k, row), device=dev, generator=gen, dtype=torch.uint8)
+    sg = (torch.randint(0, 2, (k, row), device=dev, generator=gen, dtype=torch.int8) * 2 - 1).to(torch.int8)
+    mins = (torch.rand((k, t), device=dev, generator=gen) - 0.5) * 1e-3 if codec == "rqsgd" else None
+    return (lambda out: stoch.dequantize_mean_batched(codec, lv, sg, sc, lay, 8, mins=mins, out=out),
+            lambda base, out, a, b: stoch.dequantize_mean_axpby_batched(codec, lv, sg, sc, mins, lay, 8, base, out, a,
+                                                                        b),
+            2.0)
+
+
+SYNC_DELTA_CODECS = ("slq8", "slq4", "qsgd", "rqsgd", "cnat")
+
+
+def _sync_delta_leg(sizes, k, args, dev, junk, repeats=3):
+    """One layout and K of the sync_delta leg, per codec: the fused decode-mean + axpby launch over a device-resident
+    base bucket (new output) against the route without it on the same device tensors in this process — the existing
+    decode-mean launch, then torch's (alpha * g) + (beta * m) over the flat bucket (torch's best case: three
+    launches, not three per tensor). HIP events, Infinity Cache read-flushed before every call, medians of
+    args.steps calls, `repeats` repeats, all listed. Criterion: the fused medians lie below the two-step medians by
+    more than the two-step leg's spread (max - min over its repeats)."""
+    from adfl_amd import ops
+    alpha, beta = 1.0, 1.0
+    res = {"tensors": len(sizes), "elements": int(sum(sizes)), "k": k}
+    for codec in SYNC_DELTA_CODECS:
+        lay = ops.BucketLayout(list(sizes), align=2 if codec == "slq4" else 1)   # receive_mean's compact layouts
+        gen = torch.Generator(device=dev).manual_seed(k)
+        mean, fused, row_bytes = _sync_delta_rows(codec, lay, k, dev, gen)
+        base = torch.randn(lay.total, device=dev, generator=gen)
+        out = torch.empty(lay.total, device=dev)
+        m = torch.zeros(lay.total, device=dev)
+        res2 = []
+
+        def k_fused(ev):
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            fused(base, out, alpha, beta)
+            if ev is not None:
+                ev[1].record()
+
+        def k_two_step(ev):
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            mean(m)
+            r = (alpha * base) + (beta * m)
+            if ev is not None:
+                ev[1].record()
+            res2[:] = [r]
+
+        k_fused(None), k_two_step(None)
+        torch.cuda.synchronize()
+        own = torch.zeros(lay.total, dtype=torch.bool)
+        for o, n in zip(lay.offsets.tolist(), lay.sizes.tolist()):
+            own[o:o + n] = True
+        own = own.to(dev)
+        parity = _bits_equal(out[own], res2[0][own])
+        f_ms, u_ms = [], []
+        for _ in range(repeats):
+            _, evs = timed(k_fused, args.steps, args.warmup, 1, 2)
+            f_ms.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+            _, evs = timed(k_two_step, args.steps, args.warmup, 1, 2)
+            u_ms.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+        spread = max(u_ms) - min(u_ms)
+        n = int(sum(sizes))
+        res[codec] = {"parity": parity, "fused_ms_repeats": [round(v, 4) for v in f_ms],
+                      "two_step_ms_repeats": [round(v, 4) for v in u_ms], "fused_ms": round(_median(f_ms), 4),
+                      "two_step_ms": round(_median(u_ms), 4), "two_step_spread_ms": round(spread, 4),
+                      "ratio": round(_median(u_ms) / _median(f_ms), 3),
+                      "fused_below_two_step_by_more_than_spread": bool(_median(u_ms) - _median(f_ms) > spread),
+                      # bytes the fused kernel must move per element: K payload rows, g 4, result 4
+                      "fused_frac_of_hbm_peak": round((k * row_bytes + 8) * n / (_median(f_ms) * 1e-3) / 1e9
+                                                      / HBM_PEAK_GBS, 4)}
+        del base, out, m, res2[:], mean, fused
+    return res
+
+
+def _sync_delta_host(sizes, k, steps):
+    """The whole channel call host to host on a CPU dict (ADFL's own pattern): receive_mean_axpby against
+    receive_mean followed by the reference's CPU add_parameters, wall clock, per channel class."""
+    from adfl_amd.Channel import CNATChannel, PackedSLQChannel, QSGDChannel, RQSGDChannel, SLQChannel
+    shapes = [(1, m) for m in sizes]
+    g_cpu = {f"layer{i:03d}.weight": torch.randn(sh) for i, sh in enumerate(shapes)}
+    for i in range(len(sizes)):
+        g_cpu[f"layer{i:03d}.bias"] = torch.randn(64)
+    res = {"k": k, "tensors": len(sizes)}
+
+    def wall(fn):
+        ts = []
+        for _ in range(steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return _median(ts)
+
+    for name, ch in (("slq8", SLQChannel(8)), ("slq4", PackedSLQChannel(4)), ("qsgd", QSGDChannel(8)),
+                     ("rqsgd", RQSGDChannel(8)), ("cnat", CNATChannel(8))):
+        torch.manual_seed(1)
+        ups = [ch.on_client_send({n: torch.randn(t.shape) * 1e-2 for n, t in g_cpu.items()})[0] for _ in range(k)]
+
+        def fused():
+            return ch.receive_mean_axpby(ups, g_cpu, 1.0, 1.0)[0]
+
+        def two_step():
+            agg, _ = ch.receive_mean(ups)
+            with torch.no_grad():   # add_parameters (model.py:326-334) on the same box
+                return {n: (1.0 * g_cpu[n]) + (1.0 * agg[n]) for n in agg}
+
+        a, b = fused(), two_step()
+        rec = {"parity": list(a) == list(b) and all(_bits_equal(a[n], b[n]) for n in a)}
+        del a, b
+        rec["receive_mean_axpby_ms"] = round(wall(fused), 3)
+        rec["receive_mean_then_add_parameters_ms"] = round(wall(two_step), 3)
+        rec["ratio"] = round(rec["receive_mean_then_add_parameters_ms"] / rec["receive_mean_axpby_ms"], 3)
+        res[name] = rec
+        del ups
+    return res
+
+
+def mode_sync_delta(args, world, rank, dev):
+    """The synchronous DELTA server step (Simple(CommType.DELTA, sync=True)._sync_update): the fused decode-mean +
+    axpby launch against the decode-mean launch followed by torch's statement, per codec, on the C3 layouts at
+    K = 4 and 16 and one 2^26-element tensor at K = 4, plus the whole channel call host to host on the C3 dict;
+    written to profiles/sync_delta/sync_delta.json. A leg that misses the criterion is reported as such."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    eq, lu = recipes.bucket_sizes("equal"), recipes.bucket_sizes("loguniform", 0)
+    legs = {"c3_equal_k4": _sync_delta_leg(eq, 4, args, dev, junk),
+            "c3_equal_k16": _sync_delta_leg(eq, 16, args, dev, junk),
+            "c3_loguniform_k4": _sync_delta_leg(lu, 4, args, dev, junk),
+            "c3_loguniform_k16": _sync_delta_leg(lu, 16, args, dev, junk),
+            "one_tensor_2p26_k4": _sync_delta_leg([args.elems or 1 << 26], 4, args, dev, junk)}
+    host = _sync_delta_host(eq, 4, max(3, min(args.steps, 5)))
+    flags = [leg[c]["fused_below_two_step_by_more_than_spread"] for leg in legs.values() for c in SYNC_DELTA_CODECS]
+    line = {"mode": "sync_delta", "metric": "SLQ 8 fused decode-mean + axpby, kernel alone, C3 equal layout, K = 4, "
+            "Infinity Cache flushed", "unit": "ms", "value": legs["c3_equal_k4"]["slq8"]["fused_ms"],
+            "parity": all(leg[c]["parity"] for leg in legs.values() for c in SYNC_DELTA_CODECS)
+            and all(host[c]["parity"] for c in SYNC_DELTA_CODECS),
+            "legs_meeting_criterion": f"{sum(flags)} of {len(flags)}", "steps": args.steps, "repeats": 3, **legs,
+            "host_c3_equal_k4": host}
+    out_dir = os.path.join(REPO, "profiles", "sync_delta")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "sync_delta.json"), "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    return line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1626,7 +1794,8 @@ def main():
     p.add_argument("--layout", choices=["flat", "c3_equal", "c3_loguniform"], default="flat",
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
-                                      "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch"],
+                                      "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch",
+                                      "sync_delta"],
                    required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -1645,7 +1814,8 @@ def main():
     line = {"c3": mode_c3, "c5_int4": mode_c5_int4, "exchange": mode_exchange, "pcie": mode_pcie,
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
-            "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch}[args.mode](
+            "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch,
+            "sync_delta": mode_sync_delta}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
