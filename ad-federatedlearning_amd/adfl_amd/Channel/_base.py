@@ -1,7 +1,8 @@
 """What the SLQ channels (quant.py) and the stochastic channels (stoch.py) share above the staging layer:
 ``_CodecChannel``, the class skeleton of a bi-directional codec channel (the reference's six-method surface,
 ``receive_add_``, ``receive_mean``, the synchronous DELTA server's ``receive_mean_axpby`` and the asynchronous
-server's ``receive_axpby`` / ``receive_scaled`` / ``receive_scaled_add_`` around the codec's hooks); ``_Unidirectional``, the mix-in of the
+server's ``receive_axpby`` / ``receive_scaled`` / ``receive_scaled_add_`` / ``receive_scaled_flush`` around the
+codec's hooks); ``_Unidirectional``, the mix-in of the
 uni-directional variants; and the host aggregate of the entries no device kernel takes (``_aggregate_entries``,
 ``device_mean_order_ok``).
 
@@ -424,6 +425,46 @@ class _CodecChannel(Channel):
                         t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
         return time.perf_counter() - s_time
 
+    def receive_scaled_flush(self, c_params: CompressedParameters, buffer, g_params: Parameters, factor: float,
+                             max_buffer_size: int, lr: float) -> Tuple[Parameters, float]:
+        """FedBuff's K-th client update, the one that fills the buffer (Src/ADFL/Strategy/fed_buff.py:68-100):
+        ``receive_scaled_add_(c_params, [buffer], factor)`` followed by ``flush.fedbuff_flush(buffer, g_params,
+        max_buffer_size, lr)``, bit-identical to the pair. `buffer` None or empty — K = 1, or the moment a strategy
+        would set ``self.buffer = c_update`` — stands for ``receive_scaled(c_params, factor)[0]``. Returns
+        (params_prime, seconds): keys, devices and owned storages as ``fedbuff_flush`` returns them, g_params
+        untouched.
+
+        The entries ``_apply_groups(c_params, [buffer, g_params])`` names are decoded, scaled, added to the buffer
+        in registers, averaged and stepped by one launch per device group (``_flush_payload``): their buffer
+        tensors are read and left as they were, which is the flush's documented rule (the strategy clears the
+        buffer next). Every other entry takes today's route restricted to those names: the reference add into the
+        caller's buffer tensors, then ``fedbuff_flush``."""
+        from .. import flush   # flush stages through this package
+        assert isinstance(c_params, QuantParameters)
+        names = list(c_params.params.keys())
+        has_buf = bool(buffer)
+        if has_buf:
+            assert set(buffer.keys()) == set(names)      # add_parameters_inpace, model.py:340
+        assert set(g_params.keys()) == set(names)        # add_parameters, model.py:327
+        K = flush._check_k(max_buffer_size)
+        s_time = time.perf_counter()
+        out: Parameters = {}
+        for where, ns in self._apply_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
+            outs = _flush_fused(self, c_params, ns, where, buffer if has_buf else None, g_params,
+                                lambda launch, b, g, o: launch[0](b, g, o, K, factor, lr))
+            out.update(zip(ns, outs))
+        rest = [n for n in names if n not in out]
+        if rest:
+            sub = QuantParameters({n: c_params.params[n] for n in rest}, 0)
+            if has_buf:
+                rest_buf = {n: buffer[n] for n in buffer if n not in out}
+                self.receive_scaled_add_(sub, [rest_buf], factor)
+            else:
+                rest_buf, _ = self.receive_scaled(sub, factor)
+            out.update(flush.fedbuff_flush(rest_buf, {n: g_params[n] for n in rest}, K, lr))
+        order = buffer if has_buf else c_params.params
+        return {n: out[n] for n in order}, time.perf_counter() - s_time
+
     def _apply_groups(self, c_params: QuantParameters, models):
         """The fused entries of receive_axpby / receive_scaled / receive_scaled_add_ as [("cuda" | "cpu", names)]:
         entries _receive would decode on the device (``_fusable``) whose tensor in every model of `models` is
@@ -458,6 +499,12 @@ class _CodecChannel(Channel):
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st):
         """Stage the payloads of `names` on the device: (element layout, launch), launch(bases, outs, alpha, beta)
         running the codec's fused decode + axpby over them (ops.dequantize_axpby_batched's bases / outs)."""
+        raise NotImplementedError
+
+    def _flush_payload(self, c_params: QuantParameters, names: List[str], st):
+        """``_apply_payload``'s staging of the payloads of `names`, and the codec's fused decode + accumulate + flush
+        over them: (element layout, (fedbuff, fadas)) with fedbuff(buf, g, out, K, factor, lr) and fadas(buf, g, m,
+        v, v_hat, out, K, scalars) taking ops.dequantize_fedbuff_flush_batched's operands (buf None: no buffer)."""
         raise NotImplementedError
 
     @staticmethod
@@ -509,6 +556,37 @@ def _apply_fused(channel: "_CodecChannel", c_params: QuantParameters, names: Lis
             else:
                 outs = _hand_out(out_dev, lay, shapes, [True] * len(names), st, "ax_out")
     return outs
+
+
+@_serialized
+def _flush_fused(channel: "_CodecChannel", c_params: QuantParameters, names: List[str], where: str, buffer,
+                 g_params: Parameters, run) -> List[torch.Tensor]:
+    """One fused decode + accumulate + flush over the entries `names` (receive_scaled_flush,
+    flush.FadasMoments.receive_flush): the payload staged once into an aligned bucket (``_flush_payload``), then
+    run(launch, buf side, g side, out side) with launch the codec's (fedbuff, fadas) pair:
+      where == "cuda": pointer tables straight to the buffer's and g_params' tensors, new device tensors out;
+      where == "cpu":  the buffer and g_params staged as two device buckets of the payload's layout, the result
+                       bucket handed out as owned CPU tensors — the updated buffer never exists, so the D2H of the
+                       buffer and its H2D for the flush are gone with it.
+    buffer None: no buffer. Returns the new tensors, one per name."""
+    st = _staging()
+    dev = st.device
+    lay, launch = channel._flush_payload(c_params, names, st)
+    shapes = [torch.Size(channel._apply_shape(c_params.params[n])) for n in names]
+    gs = [g_params[n] for n in names]
+    bufs = None if buffer is None else [buffer[n] for n in names]
+    with torch.no_grad():
+        if where == "cuda":
+            outs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+            run(launch, bufs, gs, outs)
+            # the next call's host gather rewrites the pinned staging this call's H2D reads from
+            torch.cuda.current_stream(dev).synchronize()
+            return outs
+        buf_dev = None if bufs is None else _stage_in(bufs, lay, st, "rf_buf", torch.float32)
+        g_dev = _stage_in(gs, lay, st, "rf_g", torch.float32)
+        out_dev = st.buf("rf_out", lay.total, torch.float32)
+        run(launch, buf_dev, g_dev, out_dev)
+        return _hand_out(out_dev, lay, shapes, [True] * len(names), st, "rf_out")
 
 
 def _mean_axpby_out(st, lay: ops.BucketLayout, shapes, bases: List[torch.Tensor], where: str, key: str, launch,

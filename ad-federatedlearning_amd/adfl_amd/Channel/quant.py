@@ -670,13 +670,27 @@ class SLQChannel(_CodecChannel):
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st: _DeviceStaging):
         """The qint8 payloads of `names` (``_fusable`` entries) in an aligned device bucket, and the fused decode
         + axpby over it (ops.dequantize_axpby_batched)."""
+        lay, q_dev, s_dev = self._stage_payload(c_params, names, st)
+        return lay, lambda bases, outs, alpha, beta: ops.dequantize_axpby_batched(q_dev, s_dev, lay, bases, outs,
+                                                                                 alpha, beta)
+
+    @staticmethod
+    def _stage_payload(c_params: QuantParameters, names: List[str], st: _DeviceStaging):
         qs = [c_params.params[n].data for n in names]
         lay = st.layout(tuple(int(q.numel()) for q in qs), align=ops.ALIGN_ELEMS)
         q_dev = _stage_in([_int8_view(q) for q in qs], lay, st, "ax_q", torch.int8)
         # q_scale() is a double; fbgemm's dequantize uses it as fp32 (quant.py:110)
         s_dev = torch.tensor([q.q_scale() for q in qs], dtype=torch.float32).to(st.device, non_blocking=True)
-        return lay, lambda bases, outs, alpha, beta: ops.dequantize_axpby_batched(q_dev, s_dev, lay, bases, outs,
-                                                                                 alpha, beta)
+        return lay, q_dev, s_dev
+
+    def _flush_payload(self, c_params: QuantParameters, names: List[str], st: _DeviceStaging):
+        """The same staged bucket, and the fused decode + accumulate + flush over it
+        (ops.dequantize_fedbuff_flush_batched / dequantize_fadas_flush_batched)."""
+        lay, q_dev, s_dev = self._stage_payload(c_params, names, st)
+        return lay, (lambda buf, g, out, K, factor, lr: ops.dequantize_fedbuff_flush_batched(
+                         q_dev, s_dev, lay, buf, g, out, K, factor, lr),
+                     lambda buf, g, m, v, h, out, K, scalars: ops.dequantize_fadas_flush_batched(
+                         q_dev, s_dev, lay, buf, g, m, v, h, out, K, scalars))
 
     @staticmethod
     def _mean_host_updates(all_c_params: List[QuantParameters], names: List[str]):
@@ -916,14 +930,27 @@ class PackedSLQChannel(SLQChannel):
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st: _DeviceStaging):
         """The packed int4 payloads of `names` in an aligned device bucket (element offsets multiples of 64, so
         tensor k's ceil(n/2) bytes start at offset / 2), and the fused unpack + decode + axpby over it."""
+        lay, p_dev, s_dev = self._stage_payload(c_params, names, st)
+        return lay, lambda bases, outs, alpha, beta: ops.dequantize_axpby_batched(p_dev, s_dev, lay, bases, outs,
+                                                                                 alpha, beta, packed=True)
+
+    @staticmethod
+    def _stage_payload(c_params: QuantParameters, names: List[str], st: _DeviceStaging):
         ps = [c_params.params[n] for n in names]
         sizes = tuple(int(torch.Size(p.shape).numel()) for p in ps)
         lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
         p_lay = st.layout(tuple((n + 1) // 2 for n in sizes), align=ops.ALIGN_ELEMS // 2)
         p_dev = _stage_in([p.data.view(torch.uint8) for p in ps], p_lay, st, "ax_p", torch.uint8)
         s_dev = torch.tensor([float(p.scale) for p in ps], dtype=torch.float32).to(st.device, non_blocking=True)
-        return lay, lambda bases, outs, alpha, beta: ops.dequantize_axpby_batched(p_dev, s_dev, lay, bases, outs,
-                                                                                 alpha, beta, packed=True)
+        return lay, p_dev, s_dev
+
+    def _flush_payload(self, c_params: QuantParameters, names: List[str], st: _DeviceStaging):
+        """The same staged packed bucket, and the fused unpack + decode + accumulate + flush over it."""
+        lay, p_dev, s_dev = self._stage_payload(c_params, names, st)
+        return lay, (lambda buf, g, out, K, factor, lr: ops.dequantize_fedbuff_flush_batched(
+                         p_dev, s_dev, lay, buf, g, out, K, factor, lr, packed=True),
+                     lambda buf, g, m, v, h, out, K, scalars: ops.dequantize_fadas_flush_batched(
+                         p_dev, s_dev, lay, buf, g, m, v, h, out, K, scalars, packed=True))
 
     @staticmethod
     def _mean_host_updates(all_c_params: List[QuantParameters], names: List[str]):

@@ -875,15 +875,28 @@ class _StochChannel(_CodecChannel):
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st):
         """Both byte planes of `names` (``_fusable`` entries) in aligned device buckets, and the fused decode +
         axpby over them (stoch.dequantize_axpby_batched)."""
+        lay, lv_dev, sg_dev, norms, mins = self._stage_payload(c_params, names, st)
+        return lay, lambda bases, outs, alpha, beta: sops.dequantize_axpby_batched(
+            self.CODEC, lv_dev, sg_dev, norms, lay, self.bits, bases, outs, alpha, beta, mins=mins)
+
+    def _stage_payload(self, c_params: QuantParameters, names: List[str], st):
         items = [(n, c_params.params[n]) for n in names]
         lay = st.layout(tuple(int(p.data.numel()) for _, p in items), align=ops.ALIGN_ELEMS)
         lv_dev = _stage_in([p.data.view(torch.uint8) for _, p in items], lay, st, "ax_levels", torch.uint8)
         sg_dev = _stage_in([p.signs.view(torch.int8) for _, p in items], lay, st, "ax_signs", torch.int8)
         sc = _scales_dev(items, self.CODEC, st.device)
         nt = len(items)
-        mins = sc[nt:] if self.CODEC == "rqsgd" else None
-        return lay, lambda bases, outs, alpha, beta: sops.dequantize_axpby_batched(
-            self.CODEC, lv_dev, sg_dev, sc[:nt], lay, self.bits, bases, outs, alpha, beta, mins=mins)
+        return lay, lv_dev, sg_dev, sc[:nt], (sc[nt:] if self.CODEC == "rqsgd" else None)
+
+    def _flush_payload(self, c_params: QuantParameters, names: List[str], st):
+        """The same staged planes, and the fused decode + accumulate + flush over them
+        (stoch.dequantize_fedbuff_flush_batched / dequantize_fadas_flush_batched)."""
+        lay, lv_dev, sg_dev, norms, mins = self._stage_payload(c_params, names, st)
+        return lay, (lambda buf, g, out, K, factor, lr: sops.dequantize_fedbuff_flush_batched(
+                         self.CODEC, lv_dev, sg_dev, norms, lay, self.bits, buf, g, out, K, factor, lr, mins=mins),
+                     lambda buf, g, m, v, h, out, K, scalars: sops.dequantize_fadas_flush_batched(
+                         self.CODEC, lv_dev, sg_dev, norms, lay, self.bits, buf, g, m, v, h, out, K, scalars,
+                         mins=mins))
 
     def _mean_payloads(self, all_c_params: List[QuantParameters], names: List[str]) -> List[torch.Tensor]:
         return _decode_mean_stoch(all_c_params, names, self.CODEC, self.bits)

@@ -10,7 +10,10 @@ Layout mirrors the reference's ``Src/ADFL`` package for the one hot path this re
 * ``adfl_amd.ops``          device-resident codec ops; ``torch.ops.adfl.*`` custom ops
 * ``adfl_amd.exchange``     one-client-per-GPU peer exchange: encode -> RCCL all-gather -> mean
 * ``adfl_amd.flush``        the buffered servers' flush: ``fedbuff_flush``, ``FadasMoments`` (``ADFL.Strategy``'s
-                            FedBuff / FADAS step on a full buffer); ``torch.ops.adfl_apply.*_flush_batched``
+                            FedBuff / FADAS step on a full buffer); ``torch.ops.adfl_apply.*_flush_batched``.
+                            The K-th client update, decode + accumulate + that flush in one launch:
+                            ``channel.receive_scaled_flush``, ``FadasMoments.receive_flush``,
+                            ``ops`` / ``stoch`` ``.dequantize_fedbuff_flush_batched`` / ``.dequantize_fadas_flush_batched``
 
 The compute lives in ``libadfl_slq.so`` (``ad-federatedlearning_amd/csrc/slq_codec.hip``, C ABI in
 ``include/adfl_slq.h``). Importing this package loads it and fails loudly if it was not built.

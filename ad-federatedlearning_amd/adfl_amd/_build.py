@@ -13,7 +13,7 @@ SOURCES = [CSRC, os.path.join(SRC_ROOT, "csrc", "slq_delta.hip"),
            os.path.join(SRC_ROOT, "csrc", "torch_norm.hip"), os.path.join(SRC_ROOT, "csrc", "qerror_ref.hip"),
            os.path.join(SRC_ROOT, "csrc", "bucket_copy.hip"), os.path.join(SRC_ROOT, "csrc", "host_stage.hip"),
            os.path.join(SRC_ROOT, "csrc", "server_flush.hip"), os.path.join(SRC_ROOT, "csrc", "host_copy.cpp")]
-DEPENDS = SOURCES + [os.path.join(SRC_ROOT, "csrc", h) for h in ("slq_device.h", "stoch_device.h", "apply_device.h","cnat_log2_table.h", "cnat_log2_dt_table.h", "philox.h", "torch_sum_order.h", "torch_norm_walk.h")]
+DEPENDS = SOURCES + [os.path.join(SRC_ROOT, "csrc", h) for h in ("slq_device.h", "stoch_device.h", "apply_device.h", "flush_device.h", "cnat_log2_table.h", "cnat_log2_dt_table.h", "philox.h", "torch_sum_order.h", "torch_norm_walk.h")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libadfl_slq.so")

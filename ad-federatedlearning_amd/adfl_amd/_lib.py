@@ -125,6 +125,16 @@ SIGNATURES = {
     # adfl_slq.h: the buffered servers' flush (csrc/server_flush.hip)
     "adfl_fedbuff_flush_batched": (INT, [P, P, P, P, I64, I32, I32, F32, P]),
     "adfl_fadas_flush_batched": (INT, [P, P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, F32, F32, F32, F32, P]),
+    # adfl_slq.h / adfl_stoch.h: the buffered servers' K-th update, fused decode + accumulate + flush
+    "adfl_slq_dequantize_fedbuff_flush_batched": (INT, [P, P, I64, P, P, P, P, I32, I32, F32, F32, P]),
+    "adfl_slq_dequantize_fedbuff_flush_batched_int4": (INT, [P, P, I64, P, P, P, P, I32, I32, F32, F32, P]),
+    "adfl_slq_dequantize_fadas_flush_batched": (INT, [P, P, I64, P, P, P, P, P, P, P, I32, I32, F32, F32, F32, F32, F32,
+                                                      F32, F32, P]),
+    "adfl_slq_dequantize_fadas_flush_batched_int4": (INT, [P, P, I64, P, P, P, P, P, P, P, I32, I32, F32, F32, F32, F32,
+                                                           F32, F32, F32, P]),
+    "adfl_stoch_dequantize_fedbuff_flush_batched": (INT, [I32, P, P, P, I64, P, P, F32, P, P, P, I32, I32, F32, F32, P]),
+    "adfl_stoch_dequantize_fadas_flush_batched": (INT, [I32, P, P, P, I64, P, P, F32, P, P, P, P, P, P, I32, I32, F32,
+                                                        F32, F32, F32, F32, F32, F32, P]),
     # adfl_host.h
     "adfl_host_copy": (INT, [P, P, P, I64, I32]),
     "adfl_host_copy_ex": (INT, [P, P, P, I64, I32, I32]),

@@ -7,7 +7,10 @@ per client update; this module is the step they feed. Both flushes are one launc
 * ``fedbuff_flush(buffer, g_params, K, lr)``  Src/ADFL/Strategy/fed_buff.py:88-92 —
   ``tensor.float().div_(K)`` then ``add_parameters(g_params, buffer, 1.0, lr)``;
 * ``FadasMoments(...).flush(buffer, g_params, K, lr_t, round)``  Strategy/fadas.py:69-73 — the same average, then
-  ``_update_amsgrad`` and ``_compute_model_step``, the moments m, v, v_hat resident on the device between rounds.
+  ``_update_amsgrad`` and ``_compute_model_step``, the moments m, v, v_hat resident on the device between rounds;
+* ``FadasMoments(...).receive_flush(channel, c_params, buffer, g_params, K, lr_t, round)`` — the K-th client update
+  and that flush in one launch (Strategy/fadas.py:56-80; FedBuff's is ``channel.receive_scaled_flush``): the payload
+  is decoded and added to the buffer in registers, so the full buffer is never written or re-read.
 
 Bit-identical to the reference's fp32 statements for FedBuff and for FADAS's moments. FADAS's ``params_prime``
 uses the correctly rounded fp32 square root; torch's CPU ``sqrt`` returns the value one ulp below it on about
@@ -254,20 +257,25 @@ class FadasMoments:
             self._init(buffer, g_params)
         if set(g_params.keys()) != set(self._order):
             raise ValueError("FadasMoments.flush: the state dict's keys changed since the first flush")
-        scalars = fadas_scalars(self.beta_1, self.beta_2, self.eps, lr_t, round)
+        out = self._step(buffer, g_params, K, fadas_scalars(self.beta_1, self.beta_2, self.eps, lr_t, round))
+        return {n: out[n] for n in self._order}
+
+    def _step(self, buffer: Parameters, g_params: Parameters, K: int, scalars: Tuple[float, ...]) -> Parameters:
+        """``flush`` over the entries of `buffer` (all of the state dict's, or the subset ``receive_flush`` hands
+        over): the entries whose moments live in the buckets through one fadas_flush_batched launch per device
+        group, the others through ``_plain_step``."""
         out: Parameters = {}
         groups = _groups(buffer, g_params)
         taken = {n for names in groups.values() for n in names}
         for n in self._fused:
-            if n not in taken or g_params[n].shape != self._shapes[self._index[n]]:
+            if n in buffer and (n not in taken or g_params[n].shape != self._shapes[self._index[n]]):
                 raise ValueError(f"FadasMoments.flush: '{n}' was fused at the first flush (its moments live in the "
                                  "device buckets) and is no longer an aligned fp32 pair of that shape on one side")
         for where, names in groups.items():
             names = [n for n in names if n in self._index]
             if not names:
                 continue
-            at = 4 * self._lay.offsets[[self._index[n] for n in names]]
-            m, v, h = (int(self._buckets[i].data_ptr()) + at for i in range(3))
+            m, v, h = self._moment_ptrs(names)
 
             def launch(lay, b, g, o, m=m, v=v, h=h):
                 fadas_flush_batched(b, g, _Ptrs(m), _Ptrs(v), _Ptrs(h), o, lay, K, scalars)
@@ -275,9 +283,86 @@ class FadasMoments:
                                              launch)))
         with torch.no_grad():
             for n in self._order:
-                if n not in out:
+                if n in buffer and n not in out:
                     out[n] = self._plain_step(n, buffer[n], g_params[n], K, scalars[4], scalars[6])
+        return out
+
+    def _moment_ptrs(self, names: List[str]):
+        """The device addresses of the moments of `names` (entries of the buckets): m, v, v_hat."""
+        at = 4 * self._lay.offsets[[self._index[n] for n in names]]
+        return tuple(int(self._buckets[i].data_ptr()) + at for i in range(3))
+
+    def receive_flush(self, channel, c_params, buffer, g_params: Parameters, max_buffer_size: int, lr_t: float,
+                      round: int, *, keep_non_fp32: bool = False) -> Parameters:
+        """FADAS's K-th client update, the one that fills the buffer (Src/ADFL/Strategy/fadas.py:56-80):
+        ``channel.receive_scaled_add_(c_params, [buffer], 1.0)`` followed by ``flush(buffer, g_params,
+        max_buffer_size, lr_t, round)``, bit-identical to the pair, m, v and v_hat included. `buffer` None or empty
+        (K = 1) stands for ``channel.receive_scaled(c_params, 1.0)[0]``. Returns params_prime as ``flush`` does.
+
+        An entry the channel fuses (``_apply_groups(c_params, [buffer, g_params])``) whose moments live in the
+        buckets is decoded, added to the buffer in registers and stepped by one launch per device group; its
+        buffer tensor is left as it was. Every other entry takes today's route: the reference add into the
+        caller's buffer tensors, then ``flush``'s launch (a passthrough bias whose moments are in the buckets) or
+        its plain statements. The first call creates the moments by ``flush``'s rule; without a buffer the decoded
+        update stands in for it: fresh fp32 tensors of the decoded shapes where the payloads live.
+
+        keep_non_fp32=True: the buffer's entries of another dtype (the int64 counter) go into the flush as they were
+        before this update, which is what ``add_parameters_inpace(buffer, update, 1, 1, to_float=True)`` leaves
+        (fadas.py:60-63: ``.float()`` copies them) and what keeping and restoring them around
+        ``receive_scaled_add_`` does."""
+        from .Channel._base import _flush_fused
+        from .model import QuantParameters
+        assert isinstance(c_params, QuantParameters)
+        names = list(c_params.params.keys())
+        has_buf = bool(buffer)
+        if has_buf:
+            assert set(buffer.keys()) == set(names)
+        assert set(g_params.keys()) == set(names)
+        K = _check_k(max_buffer_size)
+        if self._order is None:
+            self._init(buffer if has_buf else self._stand_in(channel, c_params), g_params)
+        if set(g_params.keys()) != set(self._order):
+            raise ValueError("FadasMoments.receive_flush: the state dict's keys changed since the first flush")
+        scalars = fadas_scalars(self.beta_1, self.beta_2, self.eps, lr_t, round)
+        out: Parameters = {}
+        for where, ns in channel._apply_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
+            ns = [n for n in ns if n in self._index and g_params[n].shape == self._shapes[self._index[n]]]
+            if not ns:
+                continue
+            m, v, h = self._moment_ptrs(ns)
+            outs = _flush_fused(channel, c_params, ns, where, buffer if has_buf else None, g_params,
+                                lambda launch, b, g, o, m=m, v=v, h=h: launch[1](b, g, _Ptrs(m), _Ptrs(v), _Ptrs(h),
+                                                                                o, K, scalars))
+            out.update(zip(ns, outs))
+        rest = [n for n in names if n not in out]
+        if rest:
+            sub = QuantParameters({n: c_params.params[n] for n in rest}, 0)
+            if has_buf:
+                rest_buf = {n: buffer[n] for n in buffer if n not in out}
+                keep = {n: t.clone() for n, t in rest_buf.items() if keep_non_fp32 and t.dtype != _F32}
+                channel.receive_scaled_add_(sub, [rest_buf], 1.0)
+                rest_buf.update(keep)
+            else:
+                rest_buf, _ = channel.receive_scaled(sub, 1.0)
+            out.update(self._step(rest_buf, {n: g_params[n] for n in rest}, K, scalars))
         return {n: out[n] for n in self._order}
+
+    @staticmethod
+    def _stand_in(channel, c_params) -> Parameters:
+        """What ``channel.receive_scaled(c_params, 1.0)[0]`` would hand ``_init`` at a first flush without a
+        buffer, for its classification only: the entries the channel decodes on the device as uninitialised fp32
+        tensors of the decoded shape where the payload lives, the others decoded."""
+        from .model import QuantParameters
+        like: Parameters = {}
+        other = {}
+        for n, p in c_params.params.items():
+            if channel._fusable(p):
+                like[n] = torch.empty(torch.Size(channel._apply_shape(p)), dtype=_F32, device=p.data.device)
+            else:
+                other[n] = p
+        if other:
+            like.update(channel.receive_scaled(QuantParameters(other, 0), 1.0)[0])
+        return {n: like[n] for n in c_params.params}
 
     def _plain_step(self, n: str, b: torch.Tensor, g: torch.Tensor, K: int, sqrt_bc2: float,
                     step_size: float) -> torch.Tensor:

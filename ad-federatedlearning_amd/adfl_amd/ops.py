@@ -548,6 +548,74 @@ def dequantize_axpby_batched(q: torch.Tensor, scales: torch.Tensor, layout: Buck
     # the tables may be freed on return: the caching allocator only reuses them for later work on this stream
 
 
+def flush_tables(sides, names, layout: BucketLayout, dev: torch.device):
+    """The operand tables of a fused decode + accumulate + flush launch: one device pointer (or None) per side.
+    Each side is one of flush.py's operands — a flat fp32 device bucket in `layout`, T fp32 device tensors of the
+    layout's sizes (any 4-byte alignment: a chunk that is not 16-byte aligned goes element by element) — or None
+    (the absent buffer). ValueError before anything is launched."""
+    from . import flush   # flush imports this module
+    for s, n in zip(sides, names):
+        if s is None and n != "buf":
+            raise ValueError(f"flush: {n} is required (only buf may be None)")
+    given = [(s, n) for s, n in zip(sides, names) if s is not None]
+    tab = flush._tables([s for s, _ in given], [n for _, n in given], layout, dev)
+    rows = iter(range(len(given)))
+    return tab, [None if s is None else tab[next(rows)].data_ptr() for s in sides]
+
+
+def _flush_payload(q: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, packed: bool, what: str):
+    q = _dev(q, "q")
+    if packed:
+        _require_even_offsets(layout)
+    if q.numel() * q.element_size() < ((layout.total + 1) // 2 if packed else layout.total):
+        raise ValueError(f"{what}: payload smaller than the layout")
+    return q, _f32_on(scales, layout.ntensors, q.device, "scales")
+
+
+def dequantize_fedbuff_flush_batched(q: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, buf, g, out, K: int,
+                                     factor: float, lr: float, packed: bool = False) -> None:
+    """FedBuff's K-th client update in one launch (adfl_slq_dequantize_fedbuff_flush_batched; Src/ADFL/Strategy/
+    fed_buff.py:68-100): with d = fp32(scales[t] * q_t), u = fp32(factor * d) and B = fp32(buf + u) (B = u when `buf`
+    is None: K = 1, or the update that would become the buffer),
+        out[t] = fp32(fp32(1 * g[t]) + fp32(lr * (B / K)))
+    bit-identical to dequantize_axpby_batched(q, scales, layout, buf, buf, 1.0, factor) (bases=None without a
+    buffer) followed by flush.fedbuff_flush_batched. `buf` is read and never written.
+
+    buf / g / out: flush.py's operands, each one flat fp32 device bucket in `layout` or T fp32 device tensors of
+    the layout's sizes; they must not overlap. packed=True: q is an int4-packed bucket payload (even offsets)."""
+    from .flush import _check_k
+    q, scales = _flush_payload(q, scales, layout, packed, "dequantize_fedbuff_flush_batched")
+    dev = q.device
+    K = _check_k(K)
+    tab, (b, gp, o) = flush_tables([buf, g, out], ["buf", "g", "out"], layout, dev)
+    lib = _lib.load()
+    fn = (lib.adfl_slq_dequantize_fedbuff_flush_batched_int4 if packed
+          else lib.adfl_slq_dequantize_fedbuff_flush_batched)
+    check(fn(q.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks, scales.data_ptr(), b, gp, o,
+             layout.ntensors, K, float(factor), float(lr), _stream(dev)))
+    # `tab` may be freed on return: the caching allocator only reuses it for later work on this stream
+
+
+def dequantize_fadas_flush_batched(q: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, buf, g, m, v, v_hat,
+                                   out, K: int, fadas_scalars: Sequence[float], packed: bool = False) -> None:
+    """FADAS's K-th client update in one launch (adfl_slq_dequantize_fadas_flush_batched; Src/ADFL/Strategy/
+    fadas.py:56-80): B = fp32(buf + d) (B = d when `buf` is None), then flush.fadas_flush_batched's element step on
+    B: m, v, v_hat updated in place and `out` written. Bit-identical to dequantize_axpby_batched(..., buf, buf,
+    1.0, 1.0) followed by flush.fadas_flush_batched. fadas_scalars: flush.fadas_scalars(...). Operands as
+    dequantize_fedbuff_flush_batched's."""
+    from .flush import _check_k
+    q, scales = _flush_payload(q, scales, layout, packed, "dequantize_fadas_flush_batched")
+    dev = q.device
+    K = _check_k(K)
+    if len(fadas_scalars) != 7:
+        raise ValueError("dequantize_fadas_flush_batched: scalars are flush.fadas_scalars()'s seven values")
+    tab, ptrs = flush_tables([buf, g, m, v, v_hat, out], ["buf", "g", "m", "v", "v_hat", "out"], layout, dev)
+    lib = _lib.load()
+    fn = lib.adfl_slq_dequantize_fadas_flush_batched_int4 if packed else lib.adfl_slq_dequantize_fadas_flush_batched
+    check(fn(q.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks, scales.data_ptr(), *ptrs,
+             layout.ntensors, K, *(float(s) for s in fadas_scalars), _stream(dev)))
+
+
 def dequantize_mean_batched(q_rows: torch.Tensor, scales: torch.Tensor, layout: BucketLayout, *,
                             out: Optional[torch.Tensor] = None, self_row: int = -1,
                             self_x: Optional[torch.Tensor] = None, packed: bool = False) -> torch.Tensor:
@@ -1224,3 +1292,102 @@ def slq_encode_delta_update_batched_int4_op(new: torch.Tensor, hidden: torch.Ten
 def _(new, hidden, offsets, sizes, bits):
     return (new.new_empty(((new.numel() + 1) // 2,), dtype=torch.uint8),
             new.new_empty((sizes.numel(),), dtype=torch.float32))
+
+
+# ------------------------------------------------------------------------------------------------
+# the buffered servers' K-th update over flat buckets: fused decode + accumulate + flush
+# ------------------------------------------------------------------------------------------------
+def _flush_flat(t: torch.Tensor, lay: BucketLayout, what: str) -> torch.Tensor:
+    t = t.reshape(-1)
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() < lay.total:
+        raise ValueError(f"{what} must be a contiguous float32 device bucket of >= {lay.total} elements")
+    return t
+
+
+def _fedbuff_flush_flat(q, scales, buf, g, lay: BucketLayout, K: int, factor: float, lr: float,
+                        packed: bool) -> torch.Tensor:
+    what = "slq_dequantize_fedbuff_flush_batched: "
+    g = _flush_flat(g, lay, what + "g")
+    buf = None if buf is None else _flush_flat(buf, lay, what + "buf")
+    out = _filled(g.numel(), torch.float32, g.device, lay)
+    dequantize_fedbuff_flush_batched(q.reshape(-1), scales, lay, buf, g, out, K, factor, lr, packed=packed)
+    return out
+
+
+def _fadas_flush_flat(q, scales, buf, g, m, v, v_hat, lay: BucketLayout, K: int, scalars, packed: bool) -> torch.Tensor:
+    what = "slq_dequantize_fadas_flush_batched: "
+    g = _flush_flat(g, lay, what + "g")
+    buf = None if buf is None else _flush_flat(buf, lay, what + "buf")
+    for name, t in (("m", m), ("v", v), ("v_hat", v_hat)):
+        if t.dim() != 1:
+            raise ValueError(f"{what}{name} must be one-dimensional (it is updated in place)")
+        _flush_flat(t, lay, what + name)
+    out = _filled(g.numel(), torch.float32, g.device, lay)
+    dequantize_fadas_flush_batched(q.reshape(-1), scales, lay, buf, g, m, v, v_hat, out, K, scalars, packed=packed)
+    return out
+
+
+@torch.library.custom_op("adfl_apply::slq_dequantize_fedbuff_flush_batched", mutates_args=())
+def slq_dequantize_fedbuff_flush_batched_op(q: torch.Tensor, scales: torch.Tensor, buf: Optional[torch.Tensor],
+                                            g: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, K: int,
+                                            factor: float, lr: float) -> torch.Tensor:
+    """FedBuff's K-th client update per tensor of a caller-placed layout (host int64 offsets / sizes): decode,
+    scale by `factor`, add to `buf` (None: no buffer), divide by K and step from `g`, as a new bucket shaped like
+    `g`; positions no tensor owns are zero. `buf` is not written."""
+    return _fedbuff_flush_flat(q, scales, buf, g, layout_for(offsets, sizes), K, factor, lr, False)
+
+
+@slq_dequantize_fedbuff_flush_batched_op.register_fake
+def _(q, scales, buf, g, offsets, sizes, K, factor, lr):
+    return g.new_empty((g.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_dequantize_fedbuff_flush_batched_int4", mutates_args=())
+def slq_dequantize_fedbuff_flush_batched_int4_op(packed: torch.Tensor, scales: torch.Tensor,
+                                                 buf: Optional[torch.Tensor], g: torch.Tensor, offsets: torch.Tensor,
+                                                 sizes: torch.Tensor, K: int, factor: float,
+                                                 lr: float) -> torch.Tensor:
+    """slq_dequantize_fedbuff_flush_batched over an int4-packed bucket payload (even tensor offsets)."""
+    return _fedbuff_flush_flat(packed, scales, buf, g, layout_for(offsets, sizes), K, factor, lr, True)
+
+
+@slq_dequantize_fedbuff_flush_batched_int4_op.register_fake
+def _(packed, scales, buf, g, offsets, sizes, K, factor, lr):
+    return g.new_empty((g.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_dequantize_fadas_flush_batched", mutates_args=("m", "v", "v_hat"))
+def slq_dequantize_fadas_flush_batched_op(q: torch.Tensor, scales: torch.Tensor, buf: Optional[torch.Tensor],
+                                          g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, v_hat: torch.Tensor,
+                                          offsets: torch.Tensor, sizes: torch.Tensor, K: int, beta1: float,
+                                          one_minus_beta1: float, beta2: float, one_minus_beta2: float,
+                                          sqrt_bc2: float, eps: float, step: float) -> torch.Tensor:
+    """FADAS's K-th client update per tensor of a caller-placed layout: decode, add to `buf` (None: no buffer),
+    divide by K, AMSGrad and step: m, v, v_hat (flat fp32 buckets) updated in place, the new parameters returned
+    as a bucket shaped like `g` (zero where no tensor owns). Scalars: flush.fadas_scalars()."""
+    return _fadas_flush_flat(q, scales, buf, g, m, v, v_hat, layout_for(offsets, sizes), K,
+                             (beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step), False)
+
+
+@slq_dequantize_fadas_flush_batched_op.register_fake
+def _(q, scales, buf, g, m, v, v_hat, offsets, sizes, K, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2,
+      eps, step):
+    return g.new_empty((g.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::slq_dequantize_fadas_flush_batched_int4", mutates_args=("m", "v", "v_hat"))
+def slq_dequantize_fadas_flush_batched_int4_op(packed: torch.Tensor, scales: torch.Tensor,
+                                               buf: Optional[torch.Tensor], g: torch.Tensor, m: torch.Tensor,
+                                               v: torch.Tensor, v_hat: torch.Tensor, offsets: torch.Tensor,
+                                               sizes: torch.Tensor, K: int, beta1: float, one_minus_beta1: float,
+                                               beta2: float, one_minus_beta2: float, sqrt_bc2: float, eps: float,
+                                               step: float) -> torch.Tensor:
+    """slq_dequantize_fadas_flush_batched over an int4-packed bucket payload (even tensor offsets)."""
+    return _fadas_flush_flat(packed, scales, buf, g, m, v, v_hat, layout_for(offsets, sizes), K,
+                             (beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step), True)
+
+
+@slq_dequantize_fadas_flush_batched_int4_op.register_fake
+def _(packed, scales, buf, g, m, v, v_hat, offsets, sizes, K, beta1, one_minus_beta1, beta2, one_minus_beta2,
+      sqrt_bc2, eps, step):
+    return g.new_empty((g.numel(),), dtype=torch.float32)

@@ -832,3 +832,128 @@ def stoch_decode_axpby_batched_op(levels: torch.Tensor, signs: torch.Tensor, nor
 @stoch_decode_axpby_batched_op.register_fake
 def _(levels, signs, norms, mins, base, offsets, sizes, codec, bits, alpha, beta):
     return base.new_empty((base.numel(),), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# the buffered servers' K-th update: fused decode + accumulate + flush (adfl_stoch_dequantize_*_flush_batched)
+# ------------------------------------------------------------------------------------------------
+def _flush_payload(codec: str, levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                   mins: Optional[torch.Tensor], layout: BucketLayout, bits: int):
+    """The checked payload of a fused decode + accumulate + flush: (levels, signs, norms, mins or None, s)."""
+    from .ops import _f32_on
+    _check_codec(codec)
+    levels, signs = _dev(levels, "levels"), _dev(signs, "signs")
+    dev = levels.device
+    if (levels.element_size() != 1 or signs.element_size() != 1 or levels.numel() < layout.total
+            or signs.numel() < layout.total or signs.device != dev):
+        raise ValueError(f"adfl_amd.stoch: levels / signs must be byte planes of >= {layout.total} on one device")
+    norms = _f32_on(norms, layout.ntensors, dev, "norms")
+    if codec == "rqsgd":
+        if mins is None:
+            raise ValueError("adfl_amd.stoch: RQSGD needs mins")
+        mins = _f32_on(mins, layout.ntensors, dev, "mins")
+    else:
+        mins = None
+    if codec != "cnat" and not 1 <= int(bits) <= 16:
+        raise ValueError(f"adfl_amd.stoch: bits must be in [1, 16], got {bits}")
+    s = 1.0 if codec == "cnat" else float(2 ** int(bits) - 1)   # self.levels = 2**bits - 1
+    return levels, signs, norms, mins, s
+
+
+def dequantize_fedbuff_flush_batched(codec: str, levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                     layout: BucketLayout, bits: int, buf, g, out, K: int, factor: float, lr: float,
+                                     *, mins: Optional[torch.Tensor] = None) -> None:
+    """ops.dequantize_fedbuff_flush_batched for the stochastic codecs (adfl_stoch_dequantize_fedbuff_flush_batched):
+    FedBuff's K-th client update (Src/ADFL/Strategy/fed_buff.py:68-100) in one launch, d the codec's decode of one
+    bucket payload (+0 for a tensor whose norm is 0). Bit-identical to dequantize_axpby_batched on the buffer with
+    (1.0, factor) followed by flush.fedbuff_flush_batched; `buf` (None: no buffer) is read and never written.
+    buf / g / out as ops.dequantize_fedbuff_flush_batched takes them; the payload as dequantize_axpby_batched's."""
+    from .flush import _check_k
+    from .ops import flush_tables
+    levels, signs, norms, mins, s = _flush_payload(codec, levels, signs, norms, mins, layout, bits)
+    dev = levels.device
+    K = _check_k(K)
+    tab, (b, gp, o) = flush_tables([buf, g, out], ["buf", "g", "out"], layout, dev)
+    check(_lib.load().adfl_stoch_dequantize_fedbuff_flush_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signs.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        norms.data_ptr(), mins.data_ptr() if mins is not None else None, s, b, gp, o, layout.ntensors, K,
+        float(factor), float(lr), _stream(dev)))
+
+
+def dequantize_fadas_flush_batched(codec: str, levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                   layout: BucketLayout, bits: int, buf, g, m, v, v_hat, out, K: int, fadas_scalars,
+                                   *, mins: Optional[torch.Tensor] = None) -> None:
+    """ops.dequantize_fadas_flush_batched for the stochastic codecs (adfl_stoch_dequantize_fadas_flush_batched):
+    FADAS's K-th client update (Src/ADFL/Strategy/fadas.py:56-80) in one launch; m, v, v_hat updated in place.
+    Bit-identical to dequantize_axpby_batched on the buffer with (1.0, 1.0) followed by flush.fadas_flush_batched."""
+    from .flush import _check_k
+    from .ops import flush_tables
+    levels, signs, norms, mins, s = _flush_payload(codec, levels, signs, norms, mins, layout, bits)
+    dev = levels.device
+    K = _check_k(K)
+    if len(fadas_scalars) != 7:
+        raise ValueError("dequantize_fadas_flush_batched: scalars are flush.fadas_scalars()'s seven values")
+    tab, ptrs = flush_tables([buf, g, m, v, v_hat, out], ["buf", "g", "m", "v", "v_hat", "out"], layout, dev)
+    check(_lib.load().adfl_stoch_dequantize_fadas_flush_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signs.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks,
+        norms.data_ptr(), mins.data_ptr() if mins is not None else None, s, *ptrs, layout.ntensors, K,
+        *(float(x) for x in fadas_scalars), _stream(dev)))
+
+
+@torch.library.custom_op("adfl_apply::stoch_dequantize_fedbuff_flush_batched", mutates_args=())
+def stoch_dequantize_fedbuff_flush_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                              mins: torch.Tensor, buf: Optional[torch.Tensor], g: torch.Tensor,
+                                              offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int,
+                                              K: int, factor: float, lr: float) -> torch.Tensor:
+    """FedBuff's K-th client update per tensor of stoch_encode_batched's planes (mins used by RQSGD only): decode,
+    scale by `factor`, add to `buf` (None: no buffer), divide by K and step from `g`, as a new bucket shaped like
+    `g` (positions no tensor owns are zero). `buf` is not written."""
+    from .ops import _filled, _flush_flat, layout_for
+    _check_codec(codec)
+    lay = layout_for(offsets, sizes)
+    what = "stoch_dequantize_fedbuff_flush_batched: "
+    g = _flush_flat(g, lay, what + "g")
+    buf = None if buf is None else _flush_flat(buf, lay, what + "buf")
+    out = _filled(g.numel(), torch.float32, g.device, lay)
+    dequantize_fedbuff_flush_batched(codec, levels.reshape(-1).view(torch.uint8), signs.reshape(-1), norms, lay, bits,
+                                     buf, g, out, K, factor, lr, mins=mins if codec == "rqsgd" else None)
+    return out
+
+
+@stoch_dequantize_fedbuff_flush_batched_op.register_fake
+def _(levels, signs, norms, mins, buf, g, offsets, sizes, codec, bits, K, factor, lr):
+    return g.new_empty((g.numel(),), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::stoch_dequantize_fadas_flush_batched", mutates_args=("m", "v", "v_hat"))
+def stoch_dequantize_fadas_flush_batched_op(levels: torch.Tensor, signs: torch.Tensor, norms: torch.Tensor,
+                                            mins: torch.Tensor, buf: Optional[torch.Tensor], g: torch.Tensor,
+                                            m: torch.Tensor, v: torch.Tensor, v_hat: torch.Tensor,
+                                            offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int, K: int,
+                                            beta1: float, one_minus_beta1: float, beta2: float,
+                                            one_minus_beta2: float, sqrt_bc2: float, eps: float,
+                                            step: float) -> torch.Tensor:
+    """FADAS's K-th client update per tensor of stoch_encode_batched's planes: m, v, v_hat (flat fp32 buckets)
+    updated in place, the new parameters returned as a bucket shaped like `g`. Scalars: flush.fadas_scalars()."""
+    from .ops import _filled, _flush_flat, layout_for
+    _check_codec(codec)
+    lay = layout_for(offsets, sizes)
+    what = "stoch_dequantize_fadas_flush_batched: "
+    g = _flush_flat(g, lay, what + "g")
+    buf = None if buf is None else _flush_flat(buf, lay, what + "buf")
+    for name, t in (("m", m), ("v", v), ("v_hat", v_hat)):
+        if t.dim() != 1:
+            raise ValueError(f"{what}{name} must be one-dimensional (it is updated in place)")
+        _flush_flat(t, lay, what + name)
+    out = _filled(g.numel(), torch.float32, g.device, lay)
+    dequantize_fadas_flush_batched(codec, levels.reshape(-1).view(torch.uint8), signs.reshape(-1), norms, lay, bits,
+                                   buf, g, m, v, v_hat, out, K,
+                                   (beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step),
+                                   mins=mins if codec == "rqsgd" else None)
+    return out
+
+
+@stoch_dequantize_fadas_flush_batched_op.register_fake
+def _(levels, signs, norms, mins, buf, g, m, v, v_hat, offsets, sizes, codec, bits, K, beta1, one_minus_beta1, beta2,
+      one_minus_beta2, sqrt_bc2, eps, step):
+    return g.new_empty((g.numel(),), dtype=torch.float32)

@@ -13,7 +13,7 @@
 // Cache policy, as the apply kernels (apply_device.h): the moments are updated in place with plain loads and
 // stores; buf and g are dead after the read and out is not re-read soon, so they are non-temporal.
 //
-// Arithmetic: every operation is spelled with its rounding (__fmul_rn, __fadd_rn, __fdiv_rn, __fmaf_rn), so
+// Arithmetic (the per-element functions, flush_device.h): every operation is spelled with its rounding (__fmul_rn, __fadd_rn, __fdiv_rn, __fmaf_rn), so
 // -ffp-contract decides nothing here. The square root is sqrtf: this toolchain's __fsqrt_rn expands to the
 // native, 1-ulp v_sqrt_f32 unless OCML_BASIC_ROUNDED_OPERATIONS is defined, while sqrtf (like `/`, which is
 // what __fdiv_rn expands to) is correctly rounded and keeps denormals under hipcc's default
@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "adfl_slq.h"
+#include "flush_device.h"  // the per-element functions, shared with the fused decode + accumulate + flush kernels
 
 namespace {
 
@@ -32,44 +33,6 @@ constexpr int kBlock = 256;
 constexpr int kGroups = ADFL_SLQ_CHUNK_ELEMS / 4 / kBlock;  // float4 groups per thread and chunk: 8
 constexpr int kHalf = kGroups / 2;                          // ... in flight at a time in the FADAS kernel
 static_assert(4 * kGroups * kBlock == ADFL_SLQ_CHUNK_ELEMS && 2 * kHalf == kGroups, "a chunk is two halves");
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-struct FadasScalars {
-  float k, beta1, omb1, beta2, omb2, sqrt_bc2, eps, step;
-};
-
-__device__ __forceinline__ float sqrt_rn(float x) { return sqrtf(x); }
-
-// torch.maximum: NaN when either operand is; b on a tie (the sign of a zero tie cannot arise: v' >= +0).
-__device__ __forceinline__ float maximum_nan(float a, float b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-
-__device__ __forceinline__ float fedbuff1(float buf, float g, float k, float lr) {
-  const float b = __fdiv_rn(buf, k);
-  return __fadd_rn(__fmul_rn(1.0f, g), __fmul_rn(lr, b));
-}
-
-__device__ __forceinline__ float fadas1(float buf, float g, float& m, float& v, float& vh, const FadasScalars& s) {
-  const float b = __fdiv_rn(buf, s.k);
-  m = __fmaf_rn(b, s.omb1, __fmul_rn(m, s.beta1));
-  v = __fmaf_rn(__fmul_rn(s.omb2, b), b, __fmul_rn(v, s.beta2));
-  vh = maximum_nan(vh, v);
-  const float den = __fadd_rn(__fdiv_rn(sqrt_rn(vh), s.sqrt_bc2), s.eps);
-  return __fadd_rn(g, __fdiv_rn(__fmul_rn(s.step, m), den));
-}
-
-__device__ __forceinline__ f4v fadas4(f4v buf, f4v g, f4v& m, f4v& v, f4v& vh, const FadasScalars& s) {
-  f4v r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float m1 = m[e], v1 = v[e], h1 = vh[e];
-    r[e] = fadas1(buf[e], g[e], m1, v1, h1, s);
-    m[e] = m1;
-    v[e] = v1;
-    vh[e] = h1;
-  }
-  return r;
-}
 
 __device__ __forceinline__ bool aligned16(const void* a, const void* b, const void* c) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;

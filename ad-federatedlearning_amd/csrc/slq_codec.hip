@@ -36,6 +36,7 @@
 
 #include "adfl_slq.h"
 #include "apply_device.h"  // the axpby / scale tail shared with stoch_codec.hip
+#include "flush_device.h"  // the buffered servers' per-element flush and the fused kernels' tail
 #include "slq_device.h"  // the device helpers shared with slq_delta.hip
 #include "torch_sum_order.h"
 
@@ -893,6 +894,49 @@ __global__ __launch_bounds__(kBlock) void k_dequantize_axpby_batched(const uint8
   apply_chunk(dv, grouped, c, in_tensor, a, dec1);
 }
 
+// Decode + accumulate + flush — the buffered servers' K-th client update, which fills the buffer: FedBuff's
+// tensor.float().mul_(f), add_parameters_inpace(buffer, decoded, 1, 1), div_(K) and add_parameters(g, buffer, 1, lr)
+// (Strategy/fed_buff.py:68-100) and FADAS's add, div_(K), _update_amsgrad and _compute_model_step
+// (Strategy/fadas.py:56-80) in one pass: the buffer is read, never written (flush_device.h has the arithmetic).
+// k_dequantize_axpby_batched's shape: when the tensor's offset in the bucket is a multiple of 4 and the chunk's slice
+// of every operand is 16-byte aligned (both block-uniform), the chunk's payload words are loaded up front (8 VGPRs)
+// and receive_flush_chunk walks the chunk in two halves, decoding a half's groups while its operand loads are in
+// flight. Anything else goes element by element with the same results. PACKED: an int4 bucket (pack_4bit layout,
+// even tensor offsets).
+template <bool PACKED, bool FADAS>
+__global__ __launch_bounds__(kBlock) void k_dequantize_flush_batched(const uint8_t* __restrict__ q,
+                                                                     const adfl_slq_chunk* __restrict__ chunks,
+                                                                     const float* __restrict__ scales,
+                                                                     ReceiveFlush a) {
+  static_assert(kFlushBlock == kBlock, "receive_flush_chunk's thread layout");
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const float s = scales[c.tensor];
+  const int64_t in_tensor = (int64_t)(blockIdx.x - c.first_chunk) * ADFL_SLQ_CHUNK_ELEMS;
+  const FlushSlices<FADAS> sl(a, c, in_tensor);
+  const bool vec = (c.start & 3) == 0 && sl.aligned16();
+  auto dec1 = [&](int i) -> float {
+    const int64_t e = c.start + i;
+    if (!PACKED) return s * (float)(int8_t)q[e];
+    float e0, e1;
+    dequant_byte_int4(q[e >> 1], s, e0, e1);
+    return (e & 1) ? e1 : e0;
+  };
+  uint32_t w[kFlushGroups];
+  if (vec) {
+    const int n4 = c.len >> 2;
+    const uint8_t* qc = PACKED ? q + (c.start >> 1) : q + c.start;  // 4-byte (int4: 2-byte) aligned
+#pragma unroll
+    for (int j = 0; j < kFlushGroups; ++j) {  // the payload is dead after the read
+      const int k = (int)threadIdx.x + j * kBlock;
+      w[j] = k >= n4 ? 0u
+             : PACKED ? (uint32_t)__builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(qc) + k)
+                      : __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(qc) + k);
+    }
+  }
+  receive_flush_chunk<FADAS>(
+      sl, vec, c, a, [&](int j, bool) -> float4 { return PACKED ? dequant2_int4(w[j], s) : dequant4(w[j], s); }, dec1);
+}
+
 // Quantization-error statistics of a bucket against its own payload (worker.py:186-189 computes
 // parameter_relative_mse and parameter_cosine_similarity from a full decode; here they are four sums
 // per chunk, fp64): S0 = sum (x - s*q)^2, S1 = sum x^2, S2 = sum x*(s*q), S3 = sum (s*q)^2.
@@ -1029,6 +1073,38 @@ inline bool bad_rows(int k) { return k < 1 || k > adfl_sum::kMaxRows; }
 // ================================================================================================
 // C ABI
 // ================================================================================================
+namespace {
+
+template <bool PACKED>
+int launch_fedbuff_flush(const uint8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_scales,
+                         const float* const* d_buf, const float* const* d_g, float* const* d_out, int32_t ntensors,
+                         int32_t K, float factor, float lr, void* stream) {
+  if (!d_q || !d_scales || !d_g || !d_out || receive_flush_bad_args(d_chunks, nchunks, ntensors, K)) return ADFL_E_ARG;
+  if (!aligned16(d_q)) return ADFL_E_ALIGN;
+  ReceiveFlush a{d_buf, d_g, nullptr, nullptr, nullptr, d_out, factor, lr, FadasScalars{}};
+  a.s.k = (float)K;
+  hipLaunchKernelGGL((k_dequantize_flush_batched<PACKED, false>), dim3((unsigned)nchunks), dim3(kBlock), 0,
+                     (hipStream_t)stream, d_q, d_chunks, d_scales, a);
+  return launch_status();
+}
+
+template <bool PACKED>
+int launch_fadas_flush(const uint8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_scales,
+                       const float* const* d_buf, const float* const* d_g, float* const* d_m, float* const* d_v,
+                       float* const* d_v_hat, float* const* d_out, int32_t ntensors, int32_t K,
+                       const FadasScalars& s, void* stream) {
+  if (!d_q || !d_scales || !d_g || !d_m || !d_v || !d_v_hat || !d_out ||
+      receive_flush_bad_args(d_chunks, nchunks, ntensors, K))
+    return ADFL_E_ARG;
+  if (!aligned16(d_q)) return ADFL_E_ALIGN;
+  const ReceiveFlush a{d_buf, d_g, d_m, d_v, d_v_hat, d_out, 1.0f, 0.0f, s};
+  hipLaunchKernelGGL((k_dequantize_flush_batched<PACKED, true>), dim3((unsigned)nchunks), dim3(kBlock), 0,
+                     (hipStream_t)stream, d_q, d_chunks, d_scales, a);
+  return launch_status();
+}
+
+}  // namespace
+
 extern "C" {
 
 int adfl_slq_abi_version(void) { return ADFL_SLQ_ABI_VERSION; }
@@ -1398,6 +1474,45 @@ int adfl_slq_dequantize_axpby_batched_int4(const uint8_t* d_packed, const adfl_s
   hipLaunchKernelGGL(k_dequantize_axpby_batched<true>, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream,
                      d_packed, d_chunks, d_scales, a);
   return launch_status();
+}
+
+int adfl_slq_dequantize_fedbuff_flush_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                              const float* d_scales, const float* const* d_buf,
+                                              const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                              int32_t K, float factor, float lr, void* stream) {
+  return launch_fedbuff_flush<false>(reinterpret_cast<const uint8_t*>(d_q), d_chunks, nchunks, d_scales, d_buf, d_g,
+                                     d_out, ntensors, K, factor, lr, stream);
+}
+
+int adfl_slq_dequantize_fedbuff_flush_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks,
+                                                   int64_t nchunks, const float* d_scales, const float* const* d_buf,
+                                                   const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                                   int32_t K, float factor, float lr, void* stream) {
+  return launch_fedbuff_flush<true>(d_packed, d_chunks, nchunks, d_scales, d_buf, d_g, d_out, ntensors, K, factor, lr,
+                                    stream);
+}
+
+int adfl_slq_dequantize_fadas_flush_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                            const float* d_scales, const float* const* d_buf, const float* const* d_g,
+                                            float* const* d_m, float* const* d_v, float* const* d_v_hat,
+                                            float* const* d_out, int32_t ntensors, int32_t K, float beta1,
+                                            float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
+                                            float eps, float step, void* stream) {
+  const FadasScalars s{(float)K, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step};
+  return launch_fadas_flush<false>(reinterpret_cast<const uint8_t*>(d_q), d_chunks, nchunks, d_scales, d_buf, d_g, d_m,
+                                   d_v, d_v_hat, d_out, ntensors, K, s, stream);
+}
+
+int adfl_slq_dequantize_fadas_flush_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks,
+                                                 int64_t nchunks, const float* d_scales, const float* const* d_buf,
+                                                 const float* const* d_g, float* const* d_m, float* const* d_v,
+                                                 float* const* d_v_hat, float* const* d_out, int32_t ntensors,
+                                                 int32_t K, float beta1, float one_minus_beta1, float beta2,
+                                                 float one_minus_beta2, float sqrt_bc2, float eps, float step,
+                                                 void* stream) {
+  const FadasScalars s{(float)K, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step};
+  return launch_fadas_flush<true>(d_packed, d_chunks, nchunks, d_scales, d_buf, d_g, d_m, d_v, d_v_hat, d_out,
+                                  ntensors, K, s, stream);
 }
 
 int adfl_slq_dequantize_mean_int4(const uint8_t* d_packed, int64_t row_stride_bytes, int32_t k, int64_t n,

@@ -33,6 +33,7 @@
 #include "adfl_stoch.h"
 #include "apply_device.h"  // the axpby / scale tail shared with slq_codec.hip
 #include "cnat_log2_table.h"
+#include "flush_device.h"  // the buffered servers' per-element flush and the fused kernels' tail
 #include "philox.h"
 #include "stoch_device.h"
 #include "torch_norm_walk.h"
@@ -861,6 +862,51 @@ __global__ __launch_bounds__(kBlock) void k_stoch_dequantize_axpby(const uint8_t
   apply_chunk(dv, grouped, c, in_tensor, a, dec1);
 }
 
+// Decode + accumulate + flush for the three stochastic codecs — the buffered servers' K-th client update
+// (Strategy/fed_buff.py:68-100, fadas.py:56-80; slq_codec.hip k_dequantize_flush_batched is the SLQ form,
+// flush_device.h has the arithmetic). When the tensor's offset in the bucket is a multiple of 4 and the chunk's
+// slice of every operand is 16-byte aligned (both block-uniform), the chunk's level and sign dwords are loaded up
+// front (16 VGPRs) and receive_flush_chunk walks the chunk in two halves, decoding a half's groups (decode4, the
+// decode kernel's values; +0 for a tensor whose norm is 0) while its operand loads are in flight. Anything else goes
+// element by element (decode_exact) with the same results. The buffer is read, never written.
+template <int KIND, bool FADAS>
+__global__ __launch_bounds__(kBlock) void k_stoch_dequantize_flush(const uint8_t* __restrict__ levels,
+                                                                   const uint8_t* __restrict__ signs,
+                                                                   const adfl_slq_chunk* __restrict__ chunks,
+                                                                   const float* __restrict__ norms,
+                                                                   const float* __restrict__ mins, float s,
+                                                                   ReceiveFlush a) {
+  static_assert(kFlushBlock == kBlock && kFlushGroups == kPer, "receive_flush_chunk's thread layout");
+  const adfl_slq_chunk c = chunks[blockIdx.x];
+  const float norm = norms[c.tensor];
+  const float mn = KIND == 1 ? mins[c.tensor] : 0.0f;
+  const int64_t in_tensor = (int64_t)(blockIdx.x - c.first_chunk) * ADFL_SLQ_CHUNK_ELEMS;
+  const FlushSlices<FADAS> sl(a, c, in_tensor);
+  const bool vec = (c.start & 3) == 0 && sl.aligned16();
+  const uint8_t* lv = levels + c.start;
+  const uint8_t* sg = signs + c.start;
+  auto dec1 = [&](int i) -> float {  // quant.py:248-249 / :390-391 / :542-543: zeros when the norm is 0
+    return norm == 0.0f ? 0.0f : decode_exact<KIND>(lv[i], sg[i], norm, mn, s);
+  };
+  uint32_t L[kPer], G[kPer];
+  if (vec) {
+    const int n4 = c.len >> 2;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {  // both planes are dead after the read
+      const int k = (int)threadIdx.x + j * kBlock;
+      L[j] = k < n4 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(lv) + k) : 0u;
+      G[j] = k < n4 ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(sg) + k) : 0u;
+    }
+  }
+  const Div dd = make_div(s);
+  receive_flush_chunk<FADAS>(
+      sl, vec, c, a,
+      [&](int j, bool live) -> float4 {  // every lane of the half calls (a wave ballot inside decode4)
+        return norm == 0.0f ? make_float4(0.f, 0.f, 0.f, 0.f) : decode4<KIND>(L[j], G[j], norm, mn, dd, s, live);
+      },
+      dec1);
+}
+
 // Server-side mean of K clients' payloads: simple_aggregate (Src/ADFL/model.py:221-234) over the K decodes
 // (quant.py:243-252 / :385-398 / :537-545), the synchronous server's aggregate of K updates:
 //   out[i] = fp32(torch-order sum over r of d_r[i]) / K   (the division correctly rounded)
@@ -1096,6 +1142,30 @@ int adfl_stoch_detail::launch_finalize_linf(const adfl_slq_chunk* d_chunks, int6
 // ================================================================================================
 // C ABI
 // ================================================================================================
+namespace {
+
+inline bool bad_flush_payload(int32_t codec, const void* d_levels, const void* d_signs, const void* d_norms,
+                              const void* d_mins) {
+  return (codec != ADFL_CODEC_QSGD && codec != ADFL_CODEC_RQSGD && codec != ADFL_CODEC_CNAT) || !d_levels ||
+         !d_signs || !d_norms || (codec == ADFL_CODEC_RQSGD && !d_mins);
+}
+
+template <bool FADAS>
+int launch_stoch_flush(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs, const adfl_slq_chunk* d_chunks,
+                       int64_t nchunks, const float* d_norms, const float* d_mins, float s, const ReceiveFlush& a,
+                       void* stream) {
+  if (!aligned16(d_levels) || !aligned16(d_signs)) return ADFL_E_ALIGN;
+  auto kern = codec == ADFL_CODEC_QSGD    ? k_stoch_dequantize_flush<0, FADAS>
+              : codec == ADFL_CODEC_RQSGD ? k_stoch_dequantize_flush<1, FADAS>
+                                          : k_stoch_dequantize_flush<2, FADAS>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_levels,
+                     reinterpret_cast<const uint8_t*>(d_signs), d_chunks, d_norms, d_mins,
+                     codec == ADFL_CODEC_CNAT ? 1.0f : s, a);
+  return launch_status();
+}
+
+}  // namespace
+
 extern "C" {
 
 int64_t adfl_stoch_workspace_bytes(int64_t nchunks) { return nchunks < 1 ? kPartialBytes : nchunks * kPartialBytes; }
@@ -1338,6 +1408,34 @@ int adfl_stoch_dequantize_axpby_batched(int32_t codec, const uint8_t* d_levels, 
   hipLaunchKernelGGL(kern, dim3((unsigned)nchunks), dim3(kBlock), 0, (hipStream_t)stream, d_levels,
                      reinterpret_cast<const uint8_t*>(d_signs), d_chunks, d_norms, d_mins, s, a);
   return launch_status();
+}
+
+int adfl_stoch_dequantize_fedbuff_flush_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_norms,
+                                                const float* d_mins, float s, const float* const* d_buf,
+                                                const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                                int32_t K, float factor, float lr, void* stream) {
+  if (bad_flush_payload(codec, d_levels, d_signs, d_norms, d_mins) || !d_g || !d_out ||
+      receive_flush_bad_args(d_chunks, nchunks, ntensors, K))
+    return ADFL_E_ARG;
+  ReceiveFlush a{d_buf, d_g, nullptr, nullptr, nullptr, d_out, factor, lr, FadasScalars{}};
+  a.s.k = (float)K;
+  return launch_stoch_flush<false>(codec, d_levels, d_signs, d_chunks, nchunks, d_norms, d_mins, s, a, stream);
+}
+
+int adfl_stoch_dequantize_fadas_flush_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                              const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_norms,
+                                              const float* d_mins, float s, const float* const* d_buf,
+                                              const float* const* d_g, float* const* d_m, float* const* d_v,
+                                              float* const* d_v_hat, float* const* d_out, int32_t ntensors, int32_t K,
+                                              float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                                              float sqrt_bc2, float eps, float step, void* stream) {
+  if (bad_flush_payload(codec, d_levels, d_signs, d_norms, d_mins) || !d_g || !d_m || !d_v || !d_v_hat || !d_out ||
+      receive_flush_bad_args(d_chunks, nchunks, ntensors, K))
+    return ADFL_E_ARG;
+  const ReceiveFlush a{d_buf, d_g, d_m, d_v, d_v_hat, d_out, 1.0f, 0.0f,
+                       FadasScalars{(float)K, beta1, one_minus_beta1, beta2, one_minus_beta2, sqrt_bc2, eps, step}};
+  return launch_stoch_flush<true>(codec, d_levels, d_signs, d_chunks, nchunks, d_norms, d_mins, s, a, stream);
 }
 
 int adfl_philox_rounds(void) { return adfl::kPhiloxRounds; }

@@ -422,6 +422,50 @@ int adfl_fadas_flush_batched(const float* const* d_buf, const float* const* d_g,
                              float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2, float eps,
                              float step, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fused decode + accumulate + flush (csrc/slq_codec.hip): the buffered servers' K-th client update, the one that
+ * fills the buffer, in one launch. The reference's produce_update handles it in one breath: FedBuff
+ * (Src/ADFL/Strategy/fed_buff.py:68-100) scales the decoded update, adds it into the buffer, divides by K and
+ * steps; FADAS (Src/ADFL/Strategy/fadas.py:56-80) adds, divides by K, runs AMSGrad and steps; both clear the
+ * buffer straight after. Additions: ADFL_SLQ_ABI_VERSION is unchanged. Per element, with d = fp32(scale_t * q[i])
+ * (the decode's value; int4: nibble - 8 of the packed byte),
+ *   u   = fp32(factor * d)                      tensor.float().mul_(f), fed_buff.py:72-75 (FADAS: factor = 1)
+ *   B   = d_buf ? fp32(buf + u) : u             add_parameters_inpace(buffer, decoded, 1, 1), fed_buff.py:76-80
+ *   out = adfl_fedbuff_flush_batched's / adfl_fadas_flush_batched's value for the buffer element B
+ * bit-identical to adfl_slq_dequantize_axpby_batched (in place on the buffer with (1, factor), or SCALE when
+ * d_buf is NULL) followed by the flush entry above. B stays in a register: d_buf is read (non-temporally, like
+ * the payload and d_g) and never written. d_buf == NULL is "no buffer": K = 1, or the update that would become
+ * the buffer. Tables and chunk walk as the flush entries'; the payload as adfl_slq_dequantize_axpby_batched's
+ * (any tensor offsets; 16-byte accesses when the tensor's offset is a multiple of 4 elements and the chunk's
+ * slice of every table is 16-byte aligned, element by element with identical results otherwise).
+ * ADFL_E_ARG and nothing launched for a null d_q / d_scales or a null table other than d_buf, nchunks outside
+ * [1, INT32_MAX], ntensors < 1 or K < 1; ADFL_E_ALIGN for a payload base that is not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int adfl_slq_dequantize_fedbuff_flush_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                              const float* d_scales, const float* const* d_buf,
+                                              const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                              int32_t K, float factor, float lr, void* stream);
+/* Same over an int4-packed bucket payload (every tensor offset EVEN; Src/ADFL/compression.py:52-66). */
+int adfl_slq_dequantize_fedbuff_flush_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks,
+                                                   int64_t nchunks, const float* d_scales, const float* const* d_buf,
+                                                   const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                                   int32_t K, float factor, float lr, void* stream);
+/* FADAS (fadas.py:56-80): factor is 1; d_m, d_v, d_v_hat are updated in place, scalars as
+ * adfl_fadas_flush_batched's. */
+int adfl_slq_dequantize_fadas_flush_batched(const int8_t* d_q, const adfl_slq_chunk* d_chunks, int64_t nchunks,
+                                            const float* d_scales, const float* const* d_buf, const float* const* d_g,
+                                            float* const* d_m, float* const* d_v, float* const* d_v_hat,
+                                            float* const* d_out, int32_t ntensors, int32_t K, float beta1,
+                                            float one_minus_beta1, float beta2, float one_minus_beta2, float sqrt_bc2,
+                                            float eps, float step, void* stream);
+int adfl_slq_dequantize_fadas_flush_batched_int4(const uint8_t* d_packed, const adfl_slq_chunk* d_chunks,
+                                                 int64_t nchunks, const float* d_scales, const float* const* d_buf,
+                                                 const float* const* d_g, float* const* d_m, float* const* d_v,
+                                                 float* const* d_v_hat, float* const* d_out, int32_t ntensors,
+                                                 int32_t K, float beta1, float one_minus_beta1, float beta2,
+                                                 float one_minus_beta2, float sqrt_bc2, float eps, float step,
+                                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,28 @@ int adfl_stoch_dequantize_axpby_batched(int32_t codec, const uint8_t* d_levels, 
                                         float* const* d_out, int32_t ntensors, int32_t ntargets, float alpha,
                                         float beta, void* stream);
 
+/* Fused decode + accumulate + flush for the three stochastic codecs: adfl_slq_dequantize_fedbuff_flush_batched /
+ * adfl_slq_dequantize_fadas_flush_batched (adfl_slq.h) with d the codec's decode (quant.py:243-252 / :385-398 /
+ * :537-545; +0 for a tensor whose norm is 0) — the buffered servers' K-th client update, FedBuff's
+ * (Src/ADFL/Strategy/fed_buff.py:68-100) and FADAS's (Src/ADFL/Strategy/fadas.py:56-80), in one launch,
+ * bit-identical to adfl_stoch_dequantize_axpby_batched on the buffer followed by the flush entry. d_buf == NULL:
+ * no buffer. codec: ADFL_CODEC_*; s = (float)(2^bits - 1), the level count the decode divides by (QSGD / RQSGD;
+ * unused for CNAT); d_mins for RQSGD only; d_levels / d_signs 16-byte aligned (else ADFL_E_ALIGN). ADFL_E_ARG and
+ * nothing launched for an unknown codec, a null pointer or table other than d_buf, nchunks outside
+ * [1, INT32_MAX], ntensors < 1 or K < 1. */
+int adfl_stoch_dequantize_fedbuff_flush_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                                const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_norms,
+                                                const float* d_mins, float s, const float* const* d_buf,
+                                                const float* const* d_g, float* const* d_out, int32_t ntensors,
+                                                int32_t K, float factor, float lr, void* stream);
+int adfl_stoch_dequantize_fadas_flush_batched(int32_t codec, const uint8_t* d_levels, const int8_t* d_signs,
+                                              const adfl_slq_chunk* d_chunks, int64_t nchunks, const float* d_norms,
+                                              const float* d_mins, float s, const float* const* d_buf,
+                                              const float* const* d_g, float* const* d_m, float* const* d_v,
+                                              float* const* d_v_hat, float* const* d_out, int32_t ntensors, int32_t K,
+                                              float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                                              float sqrt_bc2, float eps, float step, void* stream);
+
 /* One-launch encodes (same outputs, bit for bit) for a bucket whose tensors ALL have at most
  * ADFL_SLQ_RESIDENT_CHUNKS chunks: d_work / nwork is the work list of adfl_slq_build_encode_work (the first
  * chunk of every tensor; nwork == 0 when some tensor is larger). A 1024-thread block holds one whole tensor

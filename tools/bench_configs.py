@@ -1787,6 +1787,201 @@ def mode_sync_delta(args, world, rank, dev):
     return line
 
 
+RECEIVE_FLUSH_CODECS = ("slq8", "qsgd")
+
+
+def _receive_flush_leg(sizes, args, dev, junk, repeats=3):
+    """One layout of the receive_flush leg, kernels alone: every operand one flat device bucket of the payload's
+    64-aligned layout (what the channels' host route stages; pointer tables to separate tensors run the same kernels
+    after a host-side table build, which HIP events around two launches would count against the two-call route). The
+    fused decode + accumulate + flush launch against today's two launches on the same buckets in this process — the
+    decode + axpby in place on the buffer, then the flush — for SLQ(8) and QSGD(8), FedBuff and FADAS. HIP events,
+    Infinity Cache read-flushed before every call as _flush_leg does, medians of args.steps calls, `repeats`
+    repeats, all listed. Parity: one call of each route from the same buffer and moments, `out` and the three
+    moments compared bit for bit."""
+    from adfl_amd import flush, ops, stoch
+    K, lr, factor, rnd = 10, 0.05, 6 ** -0.5, 3
+    lay = ops.BucketLayout(list(sizes), align=64)
+    gen = torch.Generator(device=dev).manual_seed(0)
+
+    def make(scale, positive=False):
+        t = torch.randn(lay.total, device=dev, generator=gen) * scale
+        return t.abs_() if positive else t
+
+    buf0, gp = make(1e-2), make(1.0)
+    m0, v0 = make(1e-3), make(1e-5, positive=True)
+    h0 = v0 * 1.5
+    sc = flush.fadas_scalars(0.9, 0.999, 1e-8, lr, rnd)
+    x = make(1e-2)
+    n_el = int(sum(sizes))
+    res = {"tensors": len(sizes), "elements": n_el, "K": K, "round": rnd}
+    for codec in RECEIVE_FLUSH_CODECS:
+        if codec == "slq8":
+            q, s = ops.encode_batched(x, lay, 8)
+            fed = lambda b, o: ops.dequantize_fedbuff_flush_batched(q, s, lay, b, gp, o, K, factor, lr)   # noqa: E731
+            fad = lambda b, m, v, h, o: ops.dequantize_fadas_flush_batched(q, s, lay, b, gp, m, v, h, o, K, sc)  # noqa: E731
+            add = lambda b, f: ops.dequantize_axpby_batched(q, s, lay, b, b, 1.0, f)   # noqa: E731
+            payload_bytes = 1
+        else:
+            lv, sg, nr = stoch.qsgd_encode_batched(x, lay, 8, seed=5, counter=0)[:3]
+            fed = lambda b, o: stoch.dequantize_fedbuff_flush_batched("qsgd", lv, sg, nr, lay, 8, b, gp, o, K, factor,   # noqa: E731
+                                                                      lr)
+            fad = lambda b, m, v, h, o: stoch.dequantize_fadas_flush_batched("qsgd", lv, sg, nr, lay, 8, b, gp, m, v, h,   # noqa: E731
+                                                                             o, K, sc)
+            add = lambda b, f: stoch.dequantize_axpby_batched("qsgd", lv, sg, nr, lay, 8, b, b, 1.0, f)   # noqa: E731
+            payload_bytes = 2
+        out_f, out_t = torch.zeros_like(gp), torch.zeros_like(gp)
+        for strategy, moved in (("fedbuff", payload_bytes + 12), ("fadas", payload_bytes + 36)):
+            fadas = strategy == "fadas"
+            bt = buf0.clone()                                    # the two-call route writes its buffer
+            mf, vf, hf = (y.clone() for y in (m0, v0, h0))
+            mt, vt, ht = (y.clone() for y in (m0, v0, h0))
+
+            def fused():
+                if fadas:
+                    fad(buf0, mf, vf, hf, out_f)
+                else:
+                    fed(buf0, out_f)
+
+            def two_calls():
+                if fadas:
+                    add(bt, 1.0)
+                    flush.fadas_flush_batched(bt, gp, mt, vt, ht, out_t, lay, K, sc)
+                else:
+                    add(bt, factor)
+                    flush.fedbuff_flush_batched(bt, gp, out_t, lay, K, lr)
+
+            fused(), two_calls()
+            torch.cuda.synchronize()
+            pairs = [(out_f, out_t)] + ([(mf, mt), (vf, vt), (hf, ht)] if fadas else [])
+            parity = all(_bits_equal(a, b) for a, b in pairs)
+
+            def span(body, refresh):
+                def run(ev):
+                    if refresh:   # the same buffer for every timed call, restored outside the timed span
+                        bt.copy_(buf0)
+                    junk.amax()
+                    if ev is not None:
+                        ev[0].record()
+                    body()
+                    if ev is not None:
+                        ev[1].record()
+                return run
+
+            f_ms, t_ms = [], []
+            for _ in range(repeats):
+                _, evs = timed(span(fused, False), args.steps, args.warmup, 1, 2)
+                f_ms.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+                _, evs = timed(span(two_calls, True), args.steps, args.warmup, 1, 2)
+                t_ms.append(_median([e[0].elapsed_time(e[1]) for e in evs]))
+            f, t = _median(f_ms), _median(t_ms)
+            res[f"{codec}_{strategy}"] = {
+                "parity": parity, "fused_ms_repeats": [round(v, 4) for v in f_ms],
+                "two_calls_ms_repeats": [round(v, 4) for v in t_ms], "fused_ms": round(f, 4),
+                "two_calls_ms": round(t, 4), "ratio": round(t / f, 3), "fused_faster": bool(f < t),
+                "fused_bytes_per_element": moved, "two_calls_bytes_per_element": moved + 8,
+                "fused_frac_of_hbm_peak": round(moved * n_el / (f * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+            del bt, mf, vf, hf, mt, vt, ht
+        del out_f, out_t
+    return res
+
+
+def _receive_flush_host(sizes, steps, repeats=3):
+    """The whole channel call host to host on a CPU dict (ADFL's own pattern), wall clock: receive_scaled_flush /
+    FadasMoments.receive_flush against receive_scaled_add_ followed by fedbuff_flush / FadasMoments.flush, each route
+    on its own copy of the buffer and its own moments, for SLQChannel(8) and QSGDChannel(8)."""
+    import copy
+
+    from adfl_amd import FadasMoments, fedbuff_flush
+    from adfl_amd.Channel import QSGDChannel, SLQChannel
+    K, lr, factor = 10, 0.05, 6 ** -0.5
+    g_cpu = {f"layer{i:03d}.weight": torch.randn(1, m) for i, m in enumerate(sizes)}
+    for i in range(len(sizes)):
+        g_cpu[f"layer{i:03d}.bias"] = torch.randn(64)
+    res = {"tensors": len(sizes), "K": K}
+
+    def wall(fn):
+        ts = []
+        for _ in range(steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return _median(ts)
+
+    for name, ch in (("slq8", SLQChannel(8)), ("qsgd", QSGDChannel(8))):
+        torch.manual_seed(1)
+        c = ch.on_client_send({n: torch.randn(t.shape) * 1e-2 for n, t in g_cpu.items()})[0]
+        buf0 = {n: torch.randn(t.shape) * 1e-2 for n, t in g_cpu.items()}
+        for strategy in ("fedbuff", "fadas"):
+            buf_f, buf_t = copy.deepcopy(buf0), copy.deepcopy(buf0)
+            mom_f, mom_t = FadasMoments(), FadasMoments()
+            rnd = [1, 1]
+
+            def fused(c=c):
+                if strategy == "fedbuff":
+                    return ch.receive_scaled_flush(c, buf_f, g_cpu, factor, K, lr)[0]
+                rnd[0] += 1
+                return mom_f.receive_flush(ch, c, buf_f, g_cpu, K, lr, rnd[0] - 1)
+
+            def two_calls(c=c):
+                if strategy == "fedbuff":
+                    ch.receive_scaled_add_(c, [buf_t], factor)
+                    return fedbuff_flush(buf_t, g_cpu, K, lr)
+                ch.receive_scaled_add_(c, [buf_t], 1.0)
+                rnd[1] += 1
+                return mom_t.flush(buf_t, g_cpu, K, lr, rnd[1] - 1)
+
+            # parity on copies of the payload: the reference's scaling writes a passthrough entry's own tensor
+            a, b = fused(copy.deepcopy(c)), two_calls(copy.deepcopy(c))
+            parity = list(a) == list(b) and all(_bits_equal(a[n], b[n]) for n in a)
+            if strategy == "fadas":
+                parity = parity and all(_bits_equal(x[n], y[n]) for x, y in ((mom_f.m, mom_t.m), (mom_f.v, mom_t.v),
+                                                                           (mom_f.v_hat, mom_t.v_hat)) for n in x)
+            del a, b
+            f_ms, t_ms = [], []
+            for _ in range(repeats):
+                f_ms.append(wall(fused))
+                t_ms.append(wall(two_calls))
+            f, t = _median(f_ms), _median(t_ms)
+            res[f"{name}_{strategy}"] = {"parity": parity, "fused_ms_repeats": [round(v, 3) for v in f_ms],
+                                         "two_calls_ms_repeats": [round(v, 3) for v in t_ms], "fused_ms": round(f, 3),
+                                         "two_calls_ms": round(t, 3), "ratio": round(t / f, 3),
+                                         "fused_faster": bool(f < t)}
+        del c, buf0
+    return res
+
+
+def mode_receive_flush(args, world, rank, dev):
+    """The buffered servers' K-th client update: the fused decode + accumulate + flush against today's two calls
+    (decode + axpby into the buffer, then the flush), which this change leaves untouched and which are therefore the
+    baseline, timed in this process. Kernels alone on the C3-shaped device dict and on one 2^26-element tensor, the
+    whole channel call host to host on the C3-shaped CPU dict; SLQ(8) and QSGD(8), FedBuff and FADAS; medians of 3
+    repeats. No ratio is fixed in advance: times, ratios and a parity flag per leg, written to
+    profiles/receive_flush/receive_flush.json."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    eq = list(recipes.bucket_sizes("equal"))
+    legs = {"c3_dict_device": _receive_flush_leg(eq + [64] * 256, args, dev, junk),
+            "one_tensor_2p26": _receive_flush_leg([args.elems or 1 << 26], args, dev, junk),
+            "c3_dict_host": _receive_flush_host(eq, max(3, min(args.steps, 5)))}
+    cases = [f"{c}_{s}" for c in RECEIVE_FLUSH_CODECS for s in ("fedbuff", "fadas")]
+    faster = [leg[c]["fused_faster"] for leg in legs.values() for c in cases]
+    line = {"mode": "receive_flush", "metric": "SLQ 8 fused decode + accumulate + FedBuff flush, kernel alone, "
+            "C3-shaped device dict, Infinity Cache flushed", "unit": "ms",
+            "value": legs["c3_dict_device"]["slq8_fedbuff"]["fused_ms"],
+            "parity": all(leg[c]["parity"] for leg in legs.values() for c in cases),
+            "legs_where_fused_is_faster": f"{sum(faster)} of {len(faster)}", "steps": args.steps, "repeats": 3, **legs}
+    out_dir = os.path.join(REPO, "profiles", "receive_flush")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "receive_flush.json"), "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    return line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1795,7 +1990,7 @@ def main():
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
                                       "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch",
-                                      "sync_delta"],
+                                      "sync_delta", "receive_flush"],
                    required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -1815,7 +2010,7 @@ def main():
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
             "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch,
-            "sync_delta": mode_sync_delta}[args.mode](
+            "sync_delta": mode_sync_delta, "receive_flush": mode_receive_flush}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
