@@ -152,7 +152,9 @@ class _CodecChannel(Channel):
     * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor;
     * ``_apply_payload(c_params, names, st)``: the ``_fusable`` entries' payloads staged on the device and the
       codec's fused decode + axpby over them — what receive_axpby, receive_scaled and receive_scaled_add_ (the
-      asynchronous server's update step) are written around."""
+      asynchronous server's update step) are written around;
+    * ``_flush_payload(c_params, names, st)``: the same staging with the codec's fused decode + accumulate + flush
+      (receive_scaled_flush, FadasMoments.receive_flush), for the entries ``_flush_groups`` names."""
 
     SIGN_BITS = 0    # sent per weight beside its `bits` (the stochastic codecs' sign plane: 1)
     NORM_BYTES = 4   # sent per quantized tensor: its scale or norm (RQSGD: norm + minimum factor, 8)
@@ -449,7 +451,7 @@ class _CodecChannel(Channel):
         K = flush._check_k(max_buffer_size)
         s_time = time.perf_counter()
         out: Parameters = {}
-        for where, ns in self._apply_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
+        for where, ns in self._flush_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
             outs = _flush_fused(self, c_params, ns, where, buffer if has_buf else None, g_params,
                                 lambda launch, b, g, o: launch[0](b, g, o, K, factor, lr))
             out.update(zip(ns, outs))
@@ -491,6 +493,11 @@ class _CodecChannel(Channel):
             elif not any(t.is_cuda for t in ts):
                 groups["cpu"].append(n)
         return [(w, ns) for w, ns in groups.items() if ns]
+
+    def _flush_groups(self, c_params: QuantParameters, models):
+        """The fused entries of receive_scaled_flush and flush.FadasMoments.receive_flush: ``_apply_groups``' where
+        the codec has a fused decode + accumulate + flush (``_flush_payload``); a codec without one returns []."""
+        return self._apply_groups(c_params, models)
 
     def _apply_shape(self, p: QuantParameter):
         """The decoded shape of a ``_fusable`` entry."""

@@ -44,6 +44,8 @@ from ._staging import (_DeviceStaging, _PendingD2H, _chunk_meta, _drain, _hand_o
                        _staging, phase_clock)  # noqa: F401  (phase_clock: re-exported, bench.py uses it from here)
 from .stoch import (CNATChannel, QSGDChannel, RQSGDChannel, UCNATChannel, UQSGDChannel,  # noqa: F401
                     URQSGDChannel)   # beside the SLQ channels, as in the reference (quant.py:140-570)
+from .stoch import (PackedQSGDChannel, PackedRQSGDChannel, UPackedQSGDChannel,  # noqa: F401
+                    UPackedRQSGDChannel)   # their packed wire format (bits + 1 bits per weight)
 
 
 def _host_scales(amax_bits: np.ndarray, bits: int) -> np.ndarray:

@@ -32,6 +32,10 @@ fp16 / bf16 / fp64 tensors are encoded as the reference encodes them, in their o
 op rounded to the dtype; uniforms on torch.rand's grid for the dtype): one bucket per dtype through the
 *_dt kernels (csrc/stoch_dtype.hip). Their payloads decode like fp32 ones (the reference decodes to fp32).
 
+``PackedQSGDChannel`` / ``PackedRQSGDChannel`` (and ``UPacked*``) send the payload ``simulate_bandwidth`` prices
+instead: a level plane of ``bits`` bits per weight and a sign plane of one bit per weight (csrc/stoch_packed.hip;
+fp32 tensors, bits 1-8), with the parent channel's values.
+
 This module is the stochastic codecs' side of a call: which kernels run over the bucket and how the level and
 sign planes and norms become payloads. How the bucket gets to the device and the results back into owned
 tensors is _staging.py's; the class skeleton shared with the SLQ channels (quant.py) is _base.py's.
@@ -1161,3 +1165,276 @@ class URQSGDChannel(_Unidirectional, RQSGDChannel):
 
 class UCNATChannel(_Unidirectional, CNATChannel):
     """Uni-directional CNAT (quant.py:548-570)."""
+
+
+# ------------------------------------------------------------------------------------------------
+# packed wire format: bits + 1 bits per weight (csrc/stoch_packed.hip, DESIGN.md §10 "Packed wire format")
+# ------------------------------------------------------------------------------------------------
+def _packed_layouts(st, sizes: Tuple[int, ...], bits: int):
+    """(element layout, level-byte layout, sign-byte layout) of a packed bucket: tensor offsets multiples of 64
+    elements, so tensor k's level bytes start at offset (bits > 4) or offset / 2 and its sign bytes at offset / 8 —
+    the byte layouts' own aligned offsets."""
+    lay = st.layout(sizes, align=ops.ALIGN_ELEMS)
+    nb = [sops.packed_plane_bytes(n, bits) for n in sizes]
+    lv_lay = lay if bits > 4 else st.layout(tuple(b[0] for b in nb), align=ops.ALIGN_ELEMS // 2)
+    sb_lay = st.layout(tuple(b[1] for b in nb), align=ops.ALIGN_ELEMS // 8)
+    return lay, lv_lay, sb_lay
+
+
+@_serialized
+def _encode_stoch_packed(params: Parameters, names: List[str], codec: str, bits: int, uniforms=None, seed=None,
+                         torch_norm: bool = True):
+    """_encode_stoch's payload of the ndim > 1 fp32 tensors `names`, stored in the packed format: {name: (level
+    plane, sign plane, scale, scale_2)} with 1-D uint8 planes where each input lives. The same draw from torch's
+    CPU generator, and — the uniform of an element being that of its index in the compact bucket (`_ushift_for`) —
+    the same level values and sign tests: one staging of the dict into the aligned bucket, the codec's norms, one
+    quantize launch, one copy back per plane."""
+    st = _staging()
+    dev = st.device
+    tensors = [params[n] for n in names]
+    th = _torchhost.get()
+    host_ok, numel, hptrs = th.host_bytes(tensors, 4)   # sizes, and contiguous CPU fp32 storages, in one call
+    sizes = tuple(numel.tolist())
+    lay, lv_lay, sb_lay = _packed_layouts(st, sizes, bits)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+    ushift = _ushift_for(lay, st.layout(sizes))
+    x_dev = _stage_in(tensors, lay, st, "x", torch.float32, host_ptrs=hptrs.numpy().view(np.uint64) if host_ok else None)
+    nl, ns = sops.packed_plane_bytes(lay.total, bits)
+    levels, signbits = st.buf("p_levels", nl, torch.uint8), st.buf("p_signs", ns, torch.uint8)
+    norms = st.buf("s_norms", lay.ntensors, torch.float32)
+    mins = st.buf("s_mins", lay.ntensors, torch.float32) if codec == "rqsgd" else None
+    ws = st.buf("stoch_ws", lay.nchunks * 16, torch.uint8)
+    sops.encode_packed_batched(codec, x_dev, lay, bits, uniforms=uniforms, ushift=ushift if ushift.any() else None,
+                               seed=seed, counter=0, levels=levels, signbits=signbits, norms=norms, mins=mins, ws=ws,
+                               torch_norm=torch_norm)
+    nm_host = st.buf("s_norms_host", 2 * lay.ntensors, torch.float32, pinned=True)
+    nm_host[:lay.ntensors].copy_(norms, non_blocking=True)
+    if mins is not None:
+        nm_host[lay.ntensors:].copy_(mins, non_blocking=True)
+    if host_ok:   # both planes' D2H enqueued at once, the owned planes of each made by native calls while they run
+        pend_lv, pend_sb = _PendingD2H(levels, lv_lay, st, "p_levels"), _PendingD2H(signbits, sb_lay, st, "p_signs")
+        n_lv, n_sb = torch.from_numpy(lv_lay.sizes), torch.from_numpy(sb_lay.sizes)
+        datas = pend_lv.finish_building(None, len(tensors), make_batch=lambda a, b: th.empty_1d(n_lv[a:b], 0))
+        signs = pend_sb.finish_building(None, len(tensors), make_batch=lambda a, b: th.empty_1d(n_sb[a:b], 0))
+    else:
+        on_cpu = [not t.is_cuda for t in tensors]
+        datas = _hand_out(levels, lv_lay, [torch.Size([n]) for n in lv_lay.sizes.tolist()], on_cpu, st, "p_levels")
+        signs = _hand_out(signbits, sb_lay, [torch.Size([n]) for n in sb_lay.sizes.tolist()], on_cpu, st, "p_signs")
+    torch.cuda.current_stream(dev).synchronize()
+    return _payloads(names, datas, signs, nm_host.tolist(), lay.ntensors, codec)
+
+
+def _stage_packed(items: List[Tuple[str, QuantParameter]], codec: str, bits: int, st, key: str):
+    """The packed planes of `items` in aligned device buckets: (element layout, levels, sign bits, norms, mins)."""
+    sizes = tuple(int(torch.Size(p.shape).numel()) for _, p in items)
+    lay, lv_lay, sb_lay = _packed_layouts(st, sizes, bits)
+    # the byte layouts' totals are the element layout's planes: lay.total (or / 2) level bytes, lay.total / 8 sign bytes
+    lv_dev = _stage_in([p.data for _, p in items], lv_lay, st, key + "_levels", torch.uint8)
+    sb_dev = _stage_in([p.signs for _, p in items], sb_lay, st, key + "_signs", torch.uint8)
+    sc = _scales_dev(items, codec, st.device)
+    nt = len(items)
+    return lay, lv_dev, sb_dev, sc[:nt], (sc[nt:] if codec == "rqsgd" else None)
+
+
+@_serialized
+def _decode_stoch_packed(items: List[Tuple[str, QuantParameter]], codec: str, bits: int) -> Dict[str, torch.Tensor]:
+    """Decode packed payloads of ndim > 1 tensors in one bucketed pass: both planes staged as they are (1.125 or
+    0.625 bytes per element over the link), one launch, owned fp32 tensors of the payloads' shapes where the
+    planes live."""
+    st = _staging()
+    lay, lv_dev, sb_dev, norms, mins = _stage_packed(items, codec, bits, st, "pd")
+    out_dev = st.buf("d_out", lay.total, torch.float32)
+    sops.dequantize_packed_batched(codec, lv_dev, sb_dev, norms, lay, bits, mins=mins, out=out_dev)
+    shapes = [torch.Size(p.shape) for _, p in items]
+    on_cpu = [not p.data.is_cuda for _, p in items]
+    if all(on_cpu):   # the owned outputs made flat by native calls while the D2H runs, then viewed in their shapes
+        n_el = torch.from_numpy(lay.sizes)
+        th = _torchhost.get()
+        flat = _PendingD2H(out_dev, lay, st, "d_out").finish_building(
+            None, len(items), make_batch=lambda a, b: th.empty_1d(n_el[a:b], 2))
+        decoded = [t.view(s) for t, s in zip(flat, shapes)]
+    else:
+        decoded = _hand_out(out_dev, lay, shapes, on_cpu, st, "d_out")
+    return {name: t for (name, _), t in zip(items, decoded)}
+
+
+class _PackedStochChannel(_StochChannel):
+    """QSGD / RQSGD with the payload the bandwidth formula prices: a level plane of ``bits`` bits per weight (one
+    byte for bits > 4, pack_4bit's nibbles for bits <= 4) and a sign plane of one bit per weight, instead of two
+    whole byte planes. Encode = the parent channel's encode (the same norms, the same draw from torch's CPU
+    generator, the same level values and sign tests: unpacking a payload gives the parent's), decode = the parent's
+    decode of the unpacked planes, bit for bit.
+
+    A coded entry is ``QuantParameter(data = 1-D uint8 level plane, bits, scale = norm, signs = 1-D uint8 sign
+    plane, shape = the tensor's shape, dtype = float32, q_dtype = uint8, scale_2 = RQSGD's minimum factor)``;
+    ``QuantParameters.size`` counts both planes' bytes. ndim <= 1 entries, empty ndim > 1 tensors and the zero-norm
+    branch's 0-dim ``scale`` are the parent's. fp32 tensors only: another ndim > 1 dtype raises
+    NotImplementedError. bits in [1, 8].
+
+    Fused here: ``receive_axpby``, ``receive_scaled`` and ``receive_scaled_add_`` (decode + axpby from the packed
+    planes, one launch). ``receive_add_``, ``receive_mean``, ``receive_mean_axpby``, ``receive_scaled_flush``,
+    ``FadasMoments.receive_flush``, ``send_delta`` and ``broadcast_delta_`` take ``_CodecChannel``'s non-fused
+    route — ``_receive`` or ``diff_parameters`` + ``_send``, then the reference's torch statements — and return
+    what the parent channel returns."""
+
+    def __init__(self, bits: int) -> None:
+        if not 1 <= bits <= 8:
+            raise ValueError(f"{self.__class__.__name__}: bits must be in [1, 8], got {bits}")
+        super().__init__(bits)
+
+    def _is_packed(self, p: QuantParameter) -> bool:
+        """A coded entry: 1-D uint8 planes of the byte counts the payload's shape gives."""
+        d, g = p.data, p.signs
+        if not (p.dtype == torch.float32 and p.q_dtype == torch.uint8 and len(p.shape) > 1
+                and isinstance(d, torch.Tensor) and isinstance(g, torch.Tensor) and d.ndim == 1 and g.ndim == 1
+                and d.dtype == torch.uint8 and g.dtype == torch.uint8 and d.is_cuda == g.is_cuda):
+            return False
+        n = torch.Size(p.shape).numel()
+        return n > 0 and (d.numel(), g.numel()) == sops.packed_plane_bytes(n, self.bits)
+
+    def _receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
+        assert isinstance(c_params, QuantParameters)
+        s_time = time.perf_counter()
+        items = list(c_params.params.items())
+        packed = [(n, p) for n, p in items if self._is_packed(p)]
+        decoded = _decode_stoch_packed(packed, self.CODEC, self.bits) if packed else {}
+        out: Parameters = {}
+        for n, p in items:
+            if n in decoded:
+                out[n] = decoded[n]
+            elif p.data.ndim > 1:   # empty tensor: the reference's scale == 0 branch
+                if p.data.numel():
+                    raise ValueError(f"{self.__class__.__name__}: '{n}' is not a packed payload entry (1-D uint8 "
+                                     f"planes of {sops.packed_plane_bytes(torch.Size(p.shape).numel(), self.bits)} "
+                                     "bytes)")
+                out[n] = torch.zeros_like(p.data, dtype=torch.float32)
+            else:
+                out[n] = p.data.data   # passthrough: q_param.data.data
+        return out, time.perf_counter() - s_time
+
+    def _fusable(self, p: QuantParameter) -> bool:
+        return self._is_packed(p)
+
+    def _passthrough(self, p: QuantParameter) -> bool:
+        return isinstance(p.data, torch.Tensor) and p.data.ndim <= 1 and not self._is_packed(p)
+
+    @staticmethod
+    def _mean_shape(p: QuantParameter):
+        return p.shape
+
+    def _stage_payload(self, c_params: QuantParameters, names: List[str], st):
+        return _stage_packed([(n, c_params.params[n]) for n in names], self.CODEC, self.bits, st, "pax")
+
+    def _apply_payload(self, c_params: QuantParameters, names: List[str], st):
+        """Both packed planes of `names` (``_fusable`` entries) in aligned device buckets, and the fused decode +
+        axpby over them (stoch.dequantize_axpby_packed_batched)."""
+        lay, lv_dev, sb_dev, norms, mins = self._stage_payload(c_params, names, st)
+        return lay, lambda bases, outs, alpha, beta: sops.dequantize_axpby_packed_batched(
+            self.CODEC, lv_dev, sb_dev, norms, lay, self.bits, bases, outs, alpha, beta, mins=mins)
+
+    # -- not fused for packed planes: the parent's hooks read two byte planes of one byte per element ---------
+    def _add_fused(self, c_params: QuantParameters, targets: List[Parameters]) -> List[str]:
+        return []
+
+    def _flush_groups(self, c_params: QuantParameters, models):
+        return []
+
+    def _mean_host_updates(self, all_c_params: List[QuantParameters], names: List[str]):
+        return None
+
+    def _mean_host_classify(self, all_c_params: List[QuantParameters], names: List[str]):
+        return None
+
+    def _mean_fused_names(self, all_c_params: List[QuantParameters], names: List[str]) -> List[str]:
+        return []
+
+    def _no_fused_form(self, *args, **kwargs):
+        raise NotImplementedError(f"{self.__class__.__name__}: no fused form over packed planes")
+
+    _decode_add = _flush_payload = _mean_payloads = _mean_apply = _quantize_delta = _no_fused_form
+
+    def receive_add_(self, c_params: CompressedParameters, targets: List[Parameters]) -> float:
+        """``_receive(c_params)`` followed by ``add_parameters_inpace(t, decoded, 1, 1, False)`` for every target:
+        the parent's results by the non-fused route."""
+        assert isinstance(c_params, QuantParameters)
+        for t in targets:
+            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
+        s_time = time.perf_counter()
+        decoded, _ = self._receive(c_params)
+        with torch.no_grad():
+            for t in targets:
+                for n, d in decoded.items():
+                    t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
+        return time.perf_counter() - s_time
+
+    def send_delta(self, params_prev: Parameters, params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``_send(diff_parameters(params_prev, params_new))`` (Src/ADFL/model.py:350-358): the parent's payload,
+        packed, in params_prev's key order, with the one draw from torch's CPU generator the parent makes."""
+        s_time = time.perf_counter()
+        assert set(params_prev.keys()) == set(params_new.keys())
+        with torch.no_grad():
+            update = {k: params_new[k] - (a if a.device == params_new[k].device else a.to(params_new[k].device))
+                      for k, a in params_prev.items()}
+        return self._quantize_params(update, self.bits), time.perf_counter() - s_time
+
+    def broadcast_delta_(self, hidden_state: Parameters,
+                         params_new: Parameters) -> Tuple[CompressedParameters, float]:
+        """``send_delta`` then ``receive_add_(c_params, [hidden_state])`` (``_CodecChannel.broadcast_delta_``)."""
+        return _CodecChannel.broadcast_delta_(self, hidden_state, params_new)
+
+    def _quantize_params(self, params: Parameters, bits: int, uniforms=None, seed=None) -> QuantParameters:
+        """Biases and running metrics (ndim <= 1) are not quantized."""
+        cls = self.__class__.__name__
+        items = list(params.items())
+        ndim, numel, is_f32, _ = (a.numpy() for a in _torchhost.get().tensor_meta([t for _, t in items]))
+        coded = (ndim > 1) & (numel > 0)
+        for i in np.nonzero(coded & ~is_f32)[0].tolist():
+            raise NotImplementedError(f"{cls}: '{items[i][0]}' is {items[i][1].dtype}; the packed planes carry fp32 "
+                                      "tensors only")
+        names = [items[i][0] for i in np.nonzero(coded)[0].tolist()]
+        if uniforms is not None and uniforms.dtype != torch.float32:
+            raise ValueError(f"{cls}: injected uniforms must be fp32, got {uniforms.dtype}")
+        encoded = (_encode_stoch_packed(params, names, self.CODEC, bits, uniforms, seed, reference_norm())
+                   if names else {})
+        qp = QuantParameter
+        pass_signs = torch.zeros(1, dtype=torch.uint8)  # passthrough entries' unused signs, one per call
+        out: Dict[str, QuantParameter] = {}
+        size = 0
+        for name, param in items:
+            e = encoded.get(name)
+            if e is not None:
+                data, signs, scale, scale_2 = e
+                out[name] = qp(data, bits, scale, signs, param.shape, param.dtype, data.dtype, scale_2)
+                size += data.nbytes + signs.nbytes
+                continue
+            if param.ndim > 1:  # empty: vector_norm is 0 -> zero branch
+                _require_codable(name, param, cls)
+                data = torch.zeros_like(param, dtype=torch.uint8)
+                out[name] = qp(data, bits, torch.tensor(0.0, dtype=param.dtype),
+                               torch.ones_like(param, dtype=torch.int8), param.shape, param.dtype, data.dtype, 0)
+            else:
+                out[name] = qp(param, bits, 0, pass_signs, param.shape, param.dtype, param.dtype, 0)
+            size += out[name].data.nbytes
+        return QuantParameters(out, size)
+
+
+class PackedQSGDChannel(_PackedStochChannel):
+    """Bi-directional QSGD on the packed wire format: QSGDChannel's values in bits + 1 bits per weight."""
+
+    CODEC = "qsgd"
+
+
+class PackedRQSGDChannel(_PackedStochChannel):
+    """Bi-directional revised QSGD on the packed wire format: RQSGDChannel's values in bits + 1 bits per weight."""
+
+    CODEC = "rqsgd"
+    NORM_BYTES = 8
+
+
+class UPackedQSGDChannel(_Unidirectional, PackedQSGDChannel):
+    """Uni-directional packed QSGD: UQSGDChannel's client -> server payload in bits + 1 bits per weight."""
+
+
+class UPackedRQSGDChannel(_Unidirectional, PackedRQSGDChannel):
+    """Uni-directional packed RQSGD: URQSGDChannel's client -> server payload in bits + 1 bits per weight."""

@@ -24,11 +24,13 @@ from . import _lib
 _lib.load()
 
 from . import compression, model, ops, stoch  # noqa: E402
-from .Channel import (Channel, CNATChannel, IdentityChannel, PackedSLQChannel, QSGDChannel,  # noqa: E402
-                      RQSGDChannel, SLQChannel, UCNATChannel, UQSGDChannel, URQSGDChannel, USLQChannel)
+from .Channel import (Channel, CNATChannel, IdentityChannel, PackedQSGDChannel, PackedRQSGDChannel,  # noqa: E402
+                      PackedSLQChannel, QSGDChannel, RQSGDChannel, SLQChannel, UCNATChannel, UPackedQSGDChannel,
+                      UPackedRQSGDChannel, UQSGDChannel, URQSGDChannel, USLQChannel)
 from . import flush  # noqa: E402  (after Channel: it stages through Channel._staging)
 from .flush import FadasMoments, fedbuff_flush  # noqa: E402
 
 __all__ = ["Channel", "IdentityChannel", "SLQChannel", "USLQChannel", "PackedSLQChannel", "QSGDChannel",
            "UQSGDChannel", "RQSGDChannel", "URQSGDChannel", "CNATChannel", "UCNATChannel", "compression", "model",
-           "ops", "stoch", "flush", "fedbuff_flush", "FadasMoments"]
+           "ops", "stoch", "flush", "fedbuff_flush", "FadasMoments", "PackedQSGDChannel", "PackedRQSGDChannel",
+           "UPackedQSGDChannel", "UPackedRQSGDChannel"]

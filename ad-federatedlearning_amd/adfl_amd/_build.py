@@ -9,7 +9,7 @@ REPO_ROOT = os.path.dirname(SRC_ROOT)
 CSRC = os.path.join(SRC_ROOT, "csrc", "slq_codec.hip")
 SOURCES = [CSRC, os.path.join(SRC_ROOT, "csrc", "slq_delta.hip"),
            os.path.join(SRC_ROOT, "csrc", "stoch_codec.hip"), os.path.join(SRC_ROOT, "csrc", "stoch_delta.hip"),
-           os.path.join(SRC_ROOT, "csrc", "stoch_dtype.hip"),
+           os.path.join(SRC_ROOT, "csrc", "stoch_dtype.hip"), os.path.join(SRC_ROOT, "csrc", "stoch_packed.hip"),
            os.path.join(SRC_ROOT, "csrc", "torch_norm.hip"), os.path.join(SRC_ROOT, "csrc", "qerror_ref.hip"),
            os.path.join(SRC_ROOT, "csrc", "bucket_copy.hip"), os.path.join(SRC_ROOT, "csrc", "host_stage.hip"),
            os.path.join(SRC_ROOT, "csrc", "server_flush.hip"), os.path.join(SRC_ROOT, "csrc", "host_copy.cpp")]

@@ -122,6 +122,10 @@ SIGNATURES = {
     "adfl_stoch_quantize_batched_dt": (INT, [I32, I32, P, P, I64, INT, P, P, U64, U64, P, P, P]),
     "adfl_stoch_encode_batched_dt": (INT, [I32, I32, P, P, I64, INT, P, U64, U64, P, I64, P, P, P, P, P]),
     "adfl_philox_uniforms_dt": (INT, [I32, P, I64, I64, U64, U64, P]),
+    # adfl_stoch.h: the packed planes, bits + 1 bits per weight (csrc/stoch_packed.hip)
+    "adfl_stoch_quantize_packed_batched": (INT, [I32, P, P, I64, INT, P, P, P, U64, U64, P, P, P]),
+    "adfl_stoch_dequantize_packed_batched": (INT, [I32, P, P, P, I64, INT, P, P, P, P]),
+    "adfl_stoch_dequantize_axpby_packed_batched": (INT, [I32, P, P, P, I64, INT, P, P, P, P, I32, I32, F32, F32, P]),
     # adfl_slq.h: the buffered servers' flush (csrc/server_flush.hip)
     "adfl_fedbuff_flush_batched": (INT, [P, P, P, P, I64, I32, I32, F32, P]),
     "adfl_fadas_flush_batched": (INT, [P, P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, F32, F32, F32, F32, P]),

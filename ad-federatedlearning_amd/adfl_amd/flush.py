@@ -325,7 +325,7 @@ class FadasMoments:
             raise ValueError("FadasMoments.receive_flush: the state dict's keys changed since the first flush")
         scalars = fadas_scalars(self.beta_1, self.beta_2, self.eps, lr_t, round)
         out: Parameters = {}
-        for where, ns in channel._apply_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
+        for where, ns in channel._flush_groups(c_params, [buffer, g_params] if has_buf else [g_params]):
             ns = [n for n in ns if n in self._index and g_params[n].shape == self._shapes[self._index[n]]]
             if not ns:
                 continue

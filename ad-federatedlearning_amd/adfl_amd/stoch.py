@@ -11,6 +11,9 @@ Every function takes and returns CUDA (HIP) tensors over a bucketed flat buffer 
   / ``qsgd_quantize_update_batched`` — QAFeL's broadcast: the encode that also leaves ``hidden += decode(payload)``
 * ``norms_batched`` — per-tensor ||x||_2 or (max|x|, min|x|); ``qsgd_quantize_batched`` — levels from
   given norms (what the parity tests use to inject the reference's own norm)
+* ``quantize_packed_batched`` / ``encode_packed_batched`` / ``dequantize_packed_batched`` /
+  ``dequantize_axpby_packed_batched`` — QSGD / RQSGD over the packed planes, bits + 1 bits per weight
+  (``packed_plane_bytes``; DESIGN.md §10 "Packed wire format")
 
 Randomness: pass ``uniforms`` (fp32 plane indexed like x, values in [0, 1)) to inject the reference's
 ``torch.rand_like`` draws, or leave it None to draw from the Philox4x32-7 stream ``(seed, counter)``.
@@ -34,7 +37,9 @@ __all__ = ["RngStream", "norms_batched", "qsgd_quantize_batched", "qsgd_encode_b
            "philox_uniforms", "workspace", "rqsgd_encode_delta_batched",
            "rqsgd_encode_delta_update_batched", "qsgd_quantize_update_batched",
            "torch_norms", "NORM_L2", "NORM_LINF", "NORM_L2_TORCH", "DT_DTYPES", "encode_batched_dt",
-           "quantize_batched_dt", "norms_batched_dt", "philox_uniforms_dt", "dequantize_mean_batched"]
+           "quantize_batched_dt", "norms_batched_dt", "philox_uniforms_dt", "dequantize_mean_batched",
+           "packed_plane_bytes", "quantize_packed_batched", "encode_packed_batched", "dequantize_packed_batched",
+           "dequantize_axpby_packed_batched"]
 
 
 class RngStream:
@@ -957,3 +962,231 @@ def stoch_dequantize_fadas_flush_batched_op(levels: torch.Tensor, signs: torch.T
 def _(levels, signs, norms, mins, buf, g, m, v, v_hat, offsets, sizes, codec, bits, K, beta1, one_minus_beta1, beta2,
       one_minus_beta2, sqrt_bc2, eps, step):
     return g.new_empty((g.numel(),), dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------
+# packed planes: bits + 1 bits per weight (adfl_stoch_*_packed_batched, csrc/stoch_packed.hip)
+# ------------------------------------------------------------------------------------------------
+_PACKED_CODECS = ("qsgd", "rqsgd")
+
+
+def packed_plane_bytes(n: int, bits: int) -> Tuple[int, int]:
+    """(level bytes, sign bytes) of an n-element tensor in the packed format: one level byte per element for
+    bits > 4, two levels per byte (pack_4bit's nibble order) for bits <= 4; one sign bit per element."""
+    n = int(n)
+    return (n if bits > 4 else (n + 1) // 2), (n + 7) // 8
+
+
+def _packed_args(codec: str, layout: BucketLayout, bits: int) -> Tuple[int, int]:
+    """The checks the C ABI cannot make (it never sees the chunk table): (level bytes, sign bytes) of the
+    layout's packed planes."""
+    if codec not in _PACKED_CODECS:
+        raise ValueError(f"adfl_amd.stoch: the packed planes carry {' / '.join(_PACKED_CODECS)}, got {codec!r} "
+                         "(CNAT's zero elements need a third sign state)")
+    if not 1 <= int(bits) <= 8:
+        raise ValueError(f"adfl_amd.stoch: packed planes take bits in [1, 8], got {bits}")
+    from .ops import ALIGN_ELEMS
+    if (layout.offsets % ALIGN_ELEMS).any():
+        raise ValueError(f"adfl_amd.stoch: packed planes need every tensor offset a multiple of {ALIGN_ELEMS} elements")
+    return packed_plane_bytes(layout.total, bits)
+
+
+def _packed_planes(levels: torch.Tensor, signbits: torch.Tensor, need: Tuple[int, int]):
+    """Both planes as contiguous, 16-byte aligned uint8 device tensors of at least `need` bytes on one device."""
+    for t, what in ((levels, "levels"), (signbits, "signbits")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"adfl_amd.stoch: packed {what} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+    levels, signbits = _dev(levels.reshape(-1), "levels"), _dev(signbits.reshape(-1), "signbits")
+    if signbits.device != levels.device or levels.numel() < need[0] or signbits.numel() < need[1]:
+        raise ValueError(f"adfl_amd.stoch: packed planes must hold >= {need[0]} level and >= {need[1]} sign bytes on "
+                         "one device")
+    return levels, signbits
+
+
+def _packed_scales(codec: str, norms: torch.Tensor, mins: Optional[torch.Tensor], layout: BucketLayout, dev):
+    from .ops import _f32_on
+    norms = _f32_on(norms, layout.ntensors, dev, "norms")
+    if codec != "rqsgd":
+        return norms, None
+    if mins is None:
+        raise ValueError("adfl_amd.stoch: RQSGD needs mins")
+    return norms, _f32_on(mins, layout.ntensors, dev, "mins")
+
+
+def quantize_packed_batched(codec: str, flat: torch.Tensor, layout: BucketLayout, bits: int, norms: torch.Tensor, *,
+                            uniforms: Optional[torch.Tensor] = None, ushift=None, seed: int = 0, counter: int = 0,
+                            levels: Optional[torch.Tensor] = None,
+                            signbits: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """qsgd_quantize_batched's levels and sign tests from given per-tensor norms (QSGD: L2 norms; RQSGD: max|x|),
+    stored as packed planes (packed_plane_bytes; layout offsets multiples of 64 elements): (levels, signbits),
+    uint8. ushift: per tensor, element g draws the uniform of index g + ushift[t] (rqsgd_encode_delta_batched's
+    rule: the compact bucket's draws for planes in the aligned one); injected uniforms then cover the shifted
+    layout."""
+    need = _packed_args(codec, layout, bits)
+    flat = _check_flat(flat, layout)
+    dev = flat.device
+    from .ops import _f32_on
+    norms = _f32_on(norms, layout.ntensors, dev, "norms")
+    us, us_host = _ushift(ushift, layout, dev)
+    if uniforms is not None:
+        top = int((layout.offsets + layout.sizes + us_host).max())
+        if uniforms.dtype != torch.float32 or uniforms.numel() < top:
+            raise ValueError("adfl_amd.stoch: uniforms must be an fp32 plane covering the shifted layout")
+        if not uniforms.is_cuda or not uniforms.is_contiguous() or uniforms.data_ptr() % 16:
+            raise ValueError("adfl_amd.stoch: uniforms must be a contiguous, 16-byte aligned device tensor")
+    levels = torch.empty(need[0], dtype=torch.uint8, device=dev) if levels is None else levels
+    signbits = torch.empty(need[1], dtype=torch.uint8, device=dev) if signbits is None else signbits
+    lv, sb = _packed_planes(levels, signbits, need)
+    if lv.data_ptr() != levels.data_ptr() or sb.data_ptr() != signbits.data_ptr():
+        raise ValueError("adfl_amd.stoch: packed output planes must be contiguous and 16-byte aligned")
+    check(_lib.load().adfl_stoch_quantize_packed_batched(
+        _CODEC_IDS[codec], flat.data_ptr(), layout.device_chunks(dev).data_ptr(), layout.nchunks, bits,
+        norms.data_ptr(), uniforms.data_ptr() if uniforms is not None else None,
+        us.data_ptr() if us is not None else None, seed, counter, lv.data_ptr(), sb.data_ptr(), _stream(dev)))
+    return levels, signbits
+
+
+def encode_packed_batched(codec: str, flat: torch.Tensor, layout: BucketLayout, bits: int, *,
+                          uniforms: Optional[torch.Tensor] = None, ushift=None, seed: int = 0, counter: int = 0,
+                          levels: Optional[torch.Tensor] = None, signbits: Optional[torch.Tensor] = None,
+                          norms: Optional[torch.Tensor] = None, mins: Optional[torch.Tensor] = None,
+                          ws: Optional[torch.Tensor] = None, torch_norm: bool = True):
+    """The norms the unpacked channels take (QSGD: the reference-order L2 norm, or the correctly rounded fp64 one
+    with torch_norm=False; RQSGD: max|x| and min|x|), then quantize_packed_batched: (levels, signbits, norms,
+    mins or None)."""
+    _packed_args(codec, layout, bits)
+    flat = _check_flat(flat, layout)
+    dev = flat.device
+    norms = torch.empty(layout.ntensors, dtype=torch.float32, device=dev) if norms is None else norms
+    if codec == "rqsgd":
+        norms, mins = norms_batched(flat, layout, NORM_LINF, norms=norms, mins=mins, ws=ws)
+    else:
+        mins = None
+        if torch_norm:
+            reference_norms(flat, layout, out32=norms)
+        else:
+            norms_batched(flat, layout, NORM_L2, norms=norms, ws=ws)
+    levels, signbits = quantize_packed_batched(codec, flat, layout, bits, norms, uniforms=uniforms, ushift=ushift,
+                                               seed=seed, counter=counter, levels=levels, signbits=signbits)
+    return levels, signbits, norms, mins
+
+
+def dequantize_packed_batched(codec: str, levels: torch.Tensor, signbits: torch.Tensor, norms: torch.Tensor,
+                              layout: BucketLayout, bits: int, *, mins: Optional[torch.Tensor] = None,
+                              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qsgd_decode_batched / rqsgd_decode_batched from packed planes: the fp32 bucket (layout offsets multiples of
+    64 elements), every value the unpacked decode's of the unpacked planes."""
+    need = _packed_args(codec, layout, bits)
+    levels, signbits = _packed_planes(levels, signbits, need)
+    dev = levels.device
+    norms, mins = _packed_scales(codec, norms, mins, layout, dev)
+    if out is None:
+        out = torch.empty(layout.total, dtype=torch.float32, device=dev)
+    elif (out.dtype != torch.float32 or out.device != dev or out.numel() < layout.total or not out.is_contiguous()
+          or out.data_ptr() % 16):
+        raise ValueError(f"adfl_amd.stoch: out must be a contiguous, 16-byte aligned fp32 bucket of >= {layout.total} "
+                         f"on {dev}")
+    check(_lib.load().adfl_stoch_dequantize_packed_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signbits.data_ptr(), layout.device_chunks(dev).data_ptr(),
+        layout.nchunks, bits, norms.data_ptr(), mins.data_ptr() if mins is not None else None, out.data_ptr(),
+        _stream(dev)))
+    return out
+
+
+def dequantize_axpby_packed_batched(codec: str, levels: torch.Tensor, signbits: torch.Tensor, norms: torch.Tensor,
+                                    layout: BucketLayout, bits: int, bases, outs, alpha: float, beta: float, *,
+                                    mins: Optional[torch.Tensor] = None) -> None:
+    """dequantize_axpby_batched from packed planes: the same bases / outs, arithmetic and in-place rule."""
+    from .ops import apply_tables
+    need = _packed_args(codec, layout, bits)
+    levels, signbits = _packed_planes(levels, signbits, need)
+    dev = levels.device
+    norms, mins = _packed_scales(codec, norms, mins, layout, dev)
+    b_tab, o_tab, k = apply_tables(bases, outs, layout, dev)
+    check(_lib.load().adfl_stoch_dequantize_axpby_packed_batched(
+        _CODEC_IDS[codec], levels.data_ptr(), signbits.data_ptr(), layout.device_chunks(dev).data_ptr(),
+        layout.nchunks, bits, norms.data_ptr(), mins.data_ptr() if mins is not None else None,
+        b_tab.data_ptr() if b_tab is not None else None, o_tab.data_ptr(), layout.ntensors, k, float(alpha),
+        float(beta), _stream(dev)))
+
+
+@torch.library.custom_op("adfl_apply::stoch_encode_packed_batched", mutates_args=())
+def stoch_encode_packed_batched_op(flat: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str, bits: int,
+                                   seed: int, counter: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                     torch.Tensor]:
+    """(packed levels uint8, sign bits uint8, norms f32, mins f32 — RQSGD's min|x|, else 0) of a flat fp32 buffer
+    whose tensors sit at offsets that are multiples of 64: encode_packed_batched with the Philox stream (seed,
+    counter). The planes are sized for the whole buffer (packed_plane_bytes(flat.numel(), bits)); bytes no tensor
+    owns are zero."""
+    from .ops import layout_for
+    lay = layout_for(offsets, sizes)
+    flat = flat.reshape(-1)
+    if flat.dtype != torch.float32:
+        raise ValueError(f"stoch_encode_packed_batched: fp32 buffers only, got {flat.dtype}")
+    if flat.numel() < lay.total:
+        raise ValueError("stoch_encode_packed_batched: flat buffer smaller than the layout")
+    _packed_args(codec, lay, bits)
+    nl, ns = packed_plane_bytes(flat.numel(), bits)
+    lv = torch.zeros(nl, dtype=torch.uint8, device=flat.device)
+    sb = torch.zeros(ns, dtype=torch.uint8, device=flat.device)
+    lv, sb, nr, mn = encode_packed_batched(codec, flat, lay, bits, seed=seed, counter=counter, levels=lv, signbits=sb)
+    return lv, sb, nr, (mn if mn is not None else torch.zeros(lay.ntensors, dtype=torch.float32, device=flat.device))
+
+
+@stoch_encode_packed_batched_op.register_fake
+def _(flat, offsets, sizes, codec, bits, seed, counter):
+    n, t = flat.numel(), sizes.numel()
+    nl, ns = (n if bits > 4 else (n + 1) // 2), (n + 7) // 8
+    return (flat.new_empty((nl,), dtype=torch.uint8), flat.new_empty((ns,), dtype=torch.uint8),
+            flat.new_empty((t,), dtype=torch.float32), flat.new_empty((t,), dtype=torch.float32))
+
+
+def _packed_op_total(levels: torch.Tensor, bits: int, lay: BucketLayout) -> int:
+    """The element extent a packed op's output bucket gets: what the level plane can hold, at least the layout's."""
+    n = levels.numel() if bits > 4 else 2 * levels.numel()
+    return max(int(n), lay.total)
+
+
+@torch.library.custom_op("adfl_apply::stoch_decode_packed_batched", mutates_args=())
+def stoch_decode_packed_batched_op(levels: torch.Tensor, signbits: torch.Tensor, norms: torch.Tensor,
+                                   mins: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor, codec: str,
+                                   bits: int) -> torch.Tensor:
+    """fp32 decode of stoch_encode_packed_batched's planes (mins used by RQSGD only), one float per element the
+    level plane holds (positions no tensor owns are zero)."""
+    from .ops import _filled, layout_for
+    lay = layout_for(offsets, sizes)
+    _packed_args(codec, lay, bits)
+    out = _filled(_packed_op_total(levels.reshape(-1), bits, lay), torch.float32, levels.device, lay)
+    return dequantize_packed_batched(codec, levels, signbits, norms, lay, bits, mins=mins if codec == "rqsgd" else None,
+                                     out=out)
+
+
+@stoch_decode_packed_batched_op.register_fake
+def _(levels, signbits, norms, mins, offsets, sizes, codec, bits):
+    n = levels.numel() if bits > 4 else 2 * levels.numel()
+    return levels.new_empty((n,), dtype=torch.float32)
+
+
+@torch.library.custom_op("adfl_apply::stoch_decode_axpby_packed_batched", mutates_args=())
+def stoch_decode_axpby_packed_batched_op(levels: torch.Tensor, signbits: torch.Tensor, norms: torch.Tensor,
+                                         mins: torch.Tensor, base: torch.Tensor, offsets: torch.Tensor,
+                                         sizes: torch.Tensor, codec: str, bits: int, alpha: float,
+                                         beta: float) -> torch.Tensor:
+    """fp32(fp32(alpha * base) + fp32(beta * decode)) per tensor of stoch_encode_packed_batched's planes, as a new
+    bucket shaped like `base` (mins used by RQSGD only; positions no tensor owns are zero)."""
+    from .ops import _filled, layout_for
+    lay = layout_for(offsets, sizes)
+    _packed_args(codec, lay, bits)
+    base = base.reshape(-1)
+    if base.dtype != torch.float32 or base.numel() < lay.total:
+        raise ValueError("stoch_decode_axpby_packed_batched: base must be an fp32 bucket of at least the layout's "
+                         "extent")
+    out = _filled(base.numel(), torch.float32, base.device, lay)
+    dequantize_axpby_packed_batched(codec, levels, signbits, norms, lay, bits, _dev(base, "base"), out, alpha, beta,
+                                    mins=mins if codec == "rqsgd" else None)
+    return out
+
+
+@stoch_decode_axpby_packed_batched_op.register_fake
+def _(levels, signbits, norms, mins, base, offsets, sizes, codec, bits, alpha, beta):
+    return base.new_empty((base.numel(),), dtype=torch.float32)

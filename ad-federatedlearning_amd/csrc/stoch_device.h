@@ -1,4 +1,4 @@
-// stoch_device.h — the stochastic codecs' device helpers shared by stoch_codec.hip and stoch_delta.hip: the
+// stoch_device.h — the stochastic codecs' device helpers shared by stoch_codec.hip, stoch_delta.hip and stoch_packed.hip: the
 // Philox uniforms, the QSGD / RQSGD element rules, the max / min reduction, a chunk's head / edge indexing and
 // the register quantize body. Everything is in an anonymous namespace: each translation unit gets its own copy
 // (internal linkage), as before the split. The one host entry shared across the two units is
@@ -227,11 +227,12 @@ __device__ __forceinline__ bool wave_any(bool p) { return __ballot(p) != 0ull; }
 // caller stores the sign bytes itself.
 // post(j, k, live, q): called by every lane of the wave for each group the wave reaches, with the level dword q the
 // group stores (live lanes) — the hook of the encodes that also apply the stored bytes (it may hold a ballot).
+// LV false (stoch_packed.hip's nibble levels): the level dword is not stored either, post writes its own form of q.
 struct NoPost {
   __device__ __forceinline__ void operator()(int, int, bool, uint32_t) const {}
 };
 
-template <int PB, class F, class E, class A, class P = NoPost>
+template <int PB, class F, class E, class A, class P = NoPost, bool LV = true>
 __device__ __forceinline__ void quantize_regs(const float4 (&v)[kPer], int tg, int n4, int64_t g0, const Uniforms& U,
                                               uint32_t* __restrict__ l4, uint32_t* __restrict__ s4, F fast, E exact,
                                               bool all_exact, A* acc, const uint4* pre = nullptr,
@@ -269,7 +270,7 @@ __device__ __forceinline__ void quantize_regs(const float4 (&v)[kPer], int tg, i
       if (wave_any(bad && live))
         q = pack4(exact(v[j].x, uj.x), exact(v[j].y, uj.y), exact(v[j].z, uj.z), exact(v[j].w, uj.w));
       if (live) {
-        l4[k] = q;
+        if (LV) l4[k] = q;
         if (s4) s4[k] = pack4(sign_byte(v[j].x), sign_byte(v[j].y), sign_byte(v[j].z), sign_byte(v[j].w));
         if (acc) acc->add4(v[j]);
       }

@@ -339,6 +339,51 @@ int adfl_stoch_encode_batched_dt(int32_t codec, int32_t dtype, const void* d_x, 
 int adfl_philox_uniforms_dt(int32_t dtype, void* d_out, int64_t n, int64_t start, uint64_t seed, uint64_t counter,
                             void* stream);
 
+/* ---- packed planes: bits + 1 bits per weight (csrc/stoch_packed.hip) -------------------------------------
+ * The wire format QSGDChannel / RQSGDChannel.simulate_bandwidth prices (quant.py:173-184, :313-324), for fp32
+ * buckets, ADFL_CODEC_QSGD / ADFL_CODEC_RQSGD and bits in [1, 8]. With n a tensor's element count and i an
+ * element's index in it:
+ *   sign plane   ceil(n / 8) bytes: bit i & 7 (least significant first) of byte i >> 3 is 1 exactly when the
+ *                unpacked sign byte is -1 (x < 0); 0 for x > 0, +-0, NaN and every element of a zero-norm tensor;
+ *                unused bits of the last byte are 0.
+ *   level plane  bits > 4: n bytes, the unpacked level byte. bits <= 4: ceil(n / 2) bytes, byte j =
+ *                (level[2j] << 4) | level[2j + 1] (pack_4bit's nibble order), the low nibble 0 when n is odd. A
+ *                level is at most 2^bits - 1 against the tensor's own norm; only its low 4 bits are kept.
+ * Bucket: the chunk table's tensor offsets MUST be multiples of ADFL_SLQ_ALIGN_ELEMS (64). A tensor at element
+ * offset o has its sign bytes at o / 8 and its level bytes at o (bits > 4) or o / 2 (bits <= 4); no byte is shared
+ * between tensors, and the bytes between tensors are unspecified. A chunk that breaks the rule is skipped: its
+ * bytes are neither read nor written (the library cannot see the table; adfl_amd.stoch raises instead).
+ * Decode widens a sign bit to the +1 / -1 byte and a nibble to the level byte and then computes what the unpacked
+ * entries compute: every value equals theirs on the unpacked planes bit for bit (the unpacked sign byte 0 only
+ * ever multiplies a +0 or a NaN). ADFL_SLQ_ABI_VERSION is unchanged: these are additions.
+ *
+ * Errors, nothing launched: ADFL_E_ARG for ADFL_CODEC_CNAT or an unknown codec (CNAT's zero elements decode to 0
+ * only through the sign byte 0, a third sign state this format does not have), a null pointer other than
+ * d_uniforms / d_ushift / QSGD's d_mins / d_base, nchunks outside [1, INT32_MAX], ntensors or ntargets < 1;
+ * ADFL_E_BITS for bits outside [1, 8]; ADFL_E_ALIGN for a d_x, d_uniforms, plane or d_out base that is not 16-byte
+ * aligned.
+ *
+ * Quantize given norms (QSGD: the L2 norm; RQSGD: max|x|): adfl_qsgd_quantize_batched's level values and sign
+ * tests, one launch. d_uniforms / seed / counter as there; d_ushift as adfl_rqsgd_encode_delta_batched's (per
+ * tensor, or NULL meaning 0: the element at chunk-table index g of tensor t uses uniform index g + d_ushift[t],
+ * which must not be negative), so planes in the aligned bucket carry the compact bucket's draws. Tensors with
+ * ushift % 4 != 0 draw from two Philox blocks per four elements (with injected uniforms they go element by
+ * element), with the same results. norm == 0: all-zero level and sign bytes. */
+int adfl_stoch_quantize_packed_batched(int32_t codec, const float* d_x, const adfl_slq_chunk* d_chunks,
+                                       int64_t nchunks, int bits, const float* d_norms, const float* d_uniforms,
+                                       const int64_t* d_ushift, uint64_t seed, uint64_t counter, uint8_t* d_levels,
+                                       uint8_t* d_signbits, void* stream);
+/* adfl_qsgd_dequantize_batched / adfl_rqsgd_dequantize_batched from packed planes (d_mins: RQSGD only). */
+int adfl_stoch_dequantize_packed_batched(int32_t codec, const uint8_t* d_levels, const uint8_t* d_signbits,
+                                         const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                         const float* d_norms, const float* d_mins, float* d_out, void* stream);
+/* adfl_stoch_dequantize_axpby_batched from packed planes: the same operands, arithmetic and in-place rule. */
+int adfl_stoch_dequantize_axpby_packed_batched(int32_t codec, const uint8_t* d_levels, const uint8_t* d_signbits,
+                                               const adfl_slq_chunk* d_chunks, int64_t nchunks, int bits,
+                                               const float* d_norms, const float* d_mins, const float* const* d_base,
+                                               float* const* d_out, int32_t ntensors, int32_t ntargets, float alpha,
+                                               float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,10 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
   broadcast_stoch  QAFeL's broadcast through the stochastic channels on the C3 layouts and one 2^28-element tensor
             (the protocol of `broadcast`): per codec broadcast_delta_ against send_delta + receive_add_ (wall), and in
             HIP events each fused kernel against the kernels it replaces over planes that stay on the device
+  packed_stoch  the packed QSGD wire format (bits + 1 bits per weight) against the unpacked channel and kernels in
+            one process, at 8 and 4 bits, on the C3-shaped dict and one 2^26-element tensor: device-resident
+            quantize, decode and decode + axpby (HIP events, Infinity Cache flushed, medians of --steps calls) and
+            the host-to-host encode + decode round trip (wall); a parity flag per leg
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -1982,6 +1986,159 @@ def mode_receive_flush(args, world, rank, dev):
     return line
 
 
+def _unpack_planes(lv, sb, total, bits):
+    """(level bytes, `sign byte == -1` mask) of a packed bucket's planes, by torch on the device (the format of
+    include/adfl_stoch.h, "packed planes")."""
+    idx = torch.arange(total, device=lv.device)
+    neg = ((sb[idx >> 3].to(torch.int32) >> (idx & 7).to(torch.int32)) & 1).bool()
+    if bits > 4:
+        return lv[:total], neg
+    b = lv[idx >> 1]
+    return torch.where((idx & 1) == 0, b >> 4, b & 15), neg
+
+
+def _packed_stoch_leg(sizes, bits, args, dev, junk, host_steps, repeats=3):
+    """One layout and bit width of the packed_stoch leg, QSGD: the packed kernels against the unpacked ones they
+    restate (this change leaves those untouched: they are the baseline), alternating, in one process.
+    device: quantize given norms, decode, decode + axpby over planes that stay on the device; HIP events, the
+            Infinity Cache read-flushed before every call, medians of --steps calls, the median of `repeats` rounds.
+    host:   PackedQSGDChannel against QSGDChannel, on_client_send + on_server_receive of a CPU dict, wall."""
+    from adfl_amd import ops, stoch
+    from adfl_amd.Channel import PackedQSGDChannel, QSGDChannel
+    alpha_t = 0.6 * 2 ** -0.5
+    alpha, beta = 1 - alpha_t, alpha_t
+    lay = ops.BucketLayout(list(sizes))
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(lay.total, device=dev, generator=g) * 1e-2
+    base = torch.randn(lay.total, device=dev, generator=g)
+    norms = stoch.torch_norms(x, lay)
+    nl, ns = stoch.packed_plane_bytes(lay.total, bits)
+    p_lv, p_sb = torch.empty(nl, dtype=torch.uint8, device=dev), torch.empty(ns, dtype=torch.uint8, device=dev)
+    u_lv, u_sg = torch.empty(lay.total, dtype=torch.uint8, device=dev), torch.empty(lay.total, dtype=torch.int8, device=dev)
+    out_p, out_u = torch.empty(lay.total, device=dev), torch.empty(lay.total, device=dev)
+    own = torch.zeros(lay.total, dtype=torch.bool)
+    for o, m in zip(lay.offsets.tolist(), lay.sizes.tolist()):
+        own[o:o + m] = True
+    own = own.to(dev)
+    legs = {
+        "quantize": (lambda: stoch.quantize_packed_batched("qsgd", x, lay, bits, norms, seed=7, levels=p_lv, signbits=p_sb),
+                     lambda: stoch.qsgd_quantize_batched(x, lay, bits, norms, seed=7, levels=u_lv, signs=u_sg)),
+        "decode": (lambda: stoch.dequantize_packed_batched("qsgd", p_lv, p_sb, norms, lay, bits, out=out_p),
+                   lambda: stoch.qsgd_decode_batched(u_lv, u_sg, norms, lay, bits, out=out_u)),
+        "decode_axpby": (lambda: stoch.dequantize_axpby_packed_batched("qsgd", p_lv, p_sb, norms, lay, bits, base, out_p,
+                                                                       alpha, beta),
+                         lambda: stoch.dequantize_axpby_batched("qsgd", u_lv, u_sg, norms, lay, bits, base, out_u,
+                                                                alpha, beta)),
+    }
+
+    def ev_ms(fn):
+        def step(ev):
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            fn()
+            if ev is not None:
+                ev[1].record()
+        _, evs = timed(step, args.steps, args.warmup, 1, 2)
+        return _median([e[0].elapsed_time(e[1]) for e in evs])
+
+    n = int(sum(sizes))
+    lvb = 1.0 if bits > 4 else 0.5
+    moved = {"quantize": (4 + lvb + 0.125, 6), "decode": (lvb + 0.125 + 4, 6), "decode_axpby": (lvb + 0.125 + 8, 10)}
+    res = {"tensors": len(sizes), "elements": n, "bits": bits}
+    for name, (packed, unpacked) in legs.items():
+        packed(), unpacked()
+        torch.cuda.synchronize()
+        if name == "quantize":
+            lv, neg = _unpack_planes(p_lv, p_sb, lay.total, bits)
+            parity = bool(torch.equal(lv[own], u_lv[own]) and torch.equal(neg[own], (u_sg < 0)[own]))
+            del lv, neg
+        else:
+            parity = _bits_equal(out_p[own], out_u[own])
+        tp, tu = [], []
+        for _ in range(repeats):
+            tp.append(ev_ms(packed))
+            tu.append(ev_ms(unpacked))
+        mp, mu = _median(tp), _median(tu)
+        res[name] = {"parity": parity, "packed_ms": round(mp, 4), "unpacked_ms": round(mu, 4),
+                     "packed_over_unpacked": round(mp / mu, 3), "within_1_05": bool(mp <= 1.05 * mu),
+                     "packed_bytes_per_element": moved[name][0], "unpacked_bytes_per_element": moved[name][1],
+                     "packed_frac_moved": round(moved[name][0] * n / (mp * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                     "unpacked_frac_moved": round(moved[name][1] * n / (mu * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+    del x, base, p_lv, p_sb, u_lv, u_sg, out_p, out_u, own
+
+    # host to host: ADFL's own pattern (a CPU update in, a CPU payload over the wire, CPU tensors out)
+    shapes = [(1, m) for m in sizes]
+    upd = {f"layer{i:03d}.weight": (torch.randn(sh) * 1e-2) for i, sh in enumerate(shapes)}
+    for i in range(len(sizes) if len(sizes) > 1 else 0):
+        upd[f"layer{i:03d}.bias"] = torch.randn(64) * 1e-2
+    chans = {"packed": PackedQSGDChannel(bits), "unpacked": QSGDChannel(bits)}
+    wire = {}
+
+    def round_trip(ch):
+        c, _ = ch.on_client_send(upd)
+        wire[ch.__class__.__name__] = sum(p.data.nbytes + (p.signs.nbytes if p.data.ndim > 1 or p.signs.numel() > 1 else 0)
+                                          for p in c.params.values())
+        return ch.on_server_receive(c)[0]
+
+    def wall(fn, steps):
+        ts = []
+        for _ in range(steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return _median(ts)
+
+    torch.manual_seed(3)
+    a = round_trip(chans["packed"])
+    torch.manual_seed(3)
+    b = round_trip(chans["unpacked"])
+    host = {"parity": list(a) == list(b) and all(_bits_equal(a[k], b[k]) for k in a)}
+    del a, b
+    tp, tu = [], []
+    for _ in range(repeats):
+        tp.append(wall(lambda: round_trip(chans["packed"]), host_steps))
+        tu.append(wall(lambda: round_trip(chans["unpacked"]), host_steps))
+    mp, mu = _median(tp), _median(tu)
+    host.update({"packed_ms": round(mp, 3), "unpacked_ms": round(mu, 3), "packed_over_unpacked": round(mp / mu, 3),
+                 "packed_faster": bool(mp < mu), "packed_wire_bytes": wire["PackedQSGDChannel"],
+                 "unpacked_wire_bytes": wire["QSGDChannel"]})
+    res["host_round_trip"] = host
+    return res
+
+
+def mode_packed_stoch(args, world, rank, dev):
+    """The packed QSGD wire format (bits + 1 bits per weight) against the unpacked channel and kernels, which this
+    change leaves untouched and which are therefore the baseline, timed in this process: device-resident quantize,
+    decode and decode + axpby, and the host-to-host encode + decode round trip, at 8 and 4 bits, on the C3-shaped
+    dict and on one 2^26-element tensor. Expectation: every device leg within 1.05 x its unpacked counterpart, the
+    host round trip faster; a miss is reported as such. Written to profiles/packed_stoch/packed_stoch.json."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    eq = list(recipes.bucket_sizes("equal"))
+    legs = {}
+    for bits in (8, 4):
+        legs[f"c3_dict_qsgd{bits}"] = _packed_stoch_leg(eq, bits, args, dev, junk, max(3, min(args.steps, 7)))
+        legs[f"one_tensor_2p26_qsgd{bits}"] = _packed_stoch_leg([args.elems or 1 << 26], bits, args, dev, junk, 3)
+    kernels = ("quantize", "decode", "decode_axpby")
+    within = [leg[k]["within_1_05"] for leg in legs.values() for k in kernels]
+    faster = [leg["host_round_trip"]["packed_faster"] for leg in legs.values()]
+    line = {"mode": "packed_stoch", "metric": "QSGD 8 packed decode, C3-shaped device dict, Infinity Cache flushed",
+            "unit": "ms", "value": legs["c3_dict_qsgd8"]["decode"]["packed_ms"],
+            "parity": all(leg[k]["parity"] for leg in legs.values() for k in kernels + ("host_round_trip",)),
+            "device_legs_within_1_05": f"{sum(within)} of {len(within)}",
+            "host_round_trips_faster": f"{sum(faster)} of {len(faster)}", "steps": args.steps, "repeats": 3, **legs}
+    out_dir = os.path.join(REPO, "profiles", "packed_stoch")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "packed_stoch.json"), "w") as f:
+        json.dump(line, f, indent=1)
+        f.write("\n")
+    return line
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -1990,7 +2147,7 @@ def main():
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
                                       "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch",
-                                      "sync_delta", "receive_flush"],
+                                      "sync_delta", "receive_flush", "packed_stoch"],
                    required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -2010,7 +2167,8 @@ def main():
             "channel": mode_channel, "channel_stoch": mode_channel_stoch, "stoch": mode_stoch,
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
             "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch,
-            "sync_delta": mode_sync_delta, "receive_flush": mode_receive_flush}[args.mode](
+            "sync_delta": mode_sync_delta, "receive_flush": mode_receive_flush,
+            "packed_stoch": mode_packed_stoch}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
