@@ -140,8 +140,6 @@ class _CodecChannel(Channel):
     codec's part, which a subclass supplies:
 
     * ``_quantize_params(params, bits)`` -> QuantParameters, ``_receive(c_params)`` -> (Parameters, seconds);
-    * ``_add_fused(c_params, targets)``: the entries receive_add_ decodes and adds on the device, and
-      ``_decode_add(c_params, names, targets)``, which does it;
     * ``_mean_host_updates(all_c_params, names)``: receive_mean's common case (K CPU updates of one model)
       classified in a few native calls -> (fused names, their means, the passthrough names or None), or None
       when the updates are anything else (they are then classified entry by entry, with the hooks below);
@@ -151,8 +149,9 @@ class _CodecChannel(Channel):
       and the fused decode-mean + axpby over such entries and their base tensors (receive_mean_axpby);
     * ``_passthrough(p)``: _receive hands this entry back as its own payload tensor;
     * ``_apply_payload(c_params, names, st)``: the ``_fusable`` entries' payloads staged on the device and the
-      codec's fused decode + axpby over them — what receive_axpby, receive_scaled and receive_scaled_add_ (the
-      asynchronous server's update step) are written around;
+      codec's fused decode + axpby over them — what receive_axpby, receive_scaled, receive_scaled_add_ (the
+      asynchronous server's update step) and receive_add_ (the same launch in place with alpha = beta = 1) are
+      written around;
     * ``_flush_payload(c_params, names, st)``: the same staging with the codec's fused decode + accumulate + flush
       (receive_scaled_flush, FadasMoments.receive_flush), for the entries ``_flush_groups`` names."""
 
@@ -199,24 +198,12 @@ class _CodecChannel(Channel):
         (Src/ADFL/Client/pool.py:62-75) and QAFeL's hidden-state update (Src/ADFL/Server/qafel.py:176-179),
         bit-identical to them. Returns the seconds spent.
 
-        The entries ``_add_fused`` names are decoded once on the device and added into every model there
-        (``_decode_add``: no decoded tensor crosses PCIe). Everything else takes the reference's route:
-        decode, then ``mul_(1).add_(decoded, alpha=1)``."""
-        assert isinstance(c_params, QuantParameters)
-        for t in targets:
-            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
-        s_time = time.perf_counter()
-        fused = self._add_fused(c_params, targets)
-        if fused:
-            self._decode_add(c_params, fused, targets)
-        rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in fused}, 0)
-        if rest.params:
-            decoded, _ = self.on_client_receive(rest)
-            with torch.no_grad():
-                for t in targets:
-                    for n, d in decoded.items():
-                        t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
-        return time.perf_counter() - s_time
+        The entries ``_apply_groups`` names whose targets all live on the staging device are decoded once there
+        and added into every model by the codec's fused decode + axpby launch with alpha = beta = 1
+        (``_apply_payload``: fp32(fp32(1 * t) + fp32(1 * d)) is fp32(t + d); no decoded tensor is written or crosses
+        PCIe). Everything else, CPU targets included, takes the reference's route: decode, then
+        ``mul_(1).add_(decoded, alpha=1)``."""
+        return self._add_inplace(c_params, targets, None)
 
     def broadcast_delta_(self, hidden_state: Parameters,
                          params_new: Parameters) -> Tuple[CompressedParameters, float]:
@@ -407,21 +394,31 @@ class _CodecChannel(Channel):
         ``add_parameters_inpace(t, decoded, 1, 1, False)`` (Src/ADFL/Strategy/fed_buff.py:72-80) — the later
         updates of a buffer: per element fp32(t + fp32(factor * decoded)). With factor == 1.0 it equals
         ``receive_add_``. Returns the seconds spent."""
+        return self._add_inplace(c_params, targets, factor)
+
+    def _add_inplace(self, c_params: CompressedParameters, targets: List[Parameters], factor) -> float:
+        """The one body of receive_add_ (factor None: the client's side, ``on_client_receive``, and only the
+        targets on the staging device fuse) and receive_scaled_add_ (the server's side, ``on_server_receive``, the
+        decoded update scaled first): ``_apply_groups``' entries by the fused in-place decode + axpby
+        (1.0, factor), the remainder by the reference's torch statements."""
         assert isinstance(c_params, QuantParameters)
         for t in targets:
             assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
         s_time = time.perf_counter()
+        scaled = factor is not None
         done = set()
         if targets:
             for where, names in self._apply_groups(c_params, targets):
-                _apply_fused(self, c_params, names, where, targets, True, 1.0, factor)
-                done.update(names)
+                if scaled or where == "cuda":
+                    _apply_fused(self, c_params, names, where, targets, True, 1.0, factor if scaled else 1.0)
+                    done.update(names)
         rest = QuantParameters({n: p for n, p in c_params.params.items() if n not in done}, 0)
         if rest.params:
-            decoded, _ = self.on_server_receive(rest)
+            decoded, _ = (self.on_server_receive if scaled else self.on_client_receive)(rest)
             with torch.no_grad():
-                for d in decoded.values():
-                    d.float().mul_(factor)
+                if scaled:
+                    for d in decoded.values():
+                        d.float().mul_(factor)
                 for t in targets:
                     for n, d in decoded.items():
                         t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
@@ -468,7 +465,8 @@ class _CodecChannel(Channel):
         return {n: out[n] for n in order}, time.perf_counter() - s_time
 
     def _apply_groups(self, c_params: QuantParameters, models):
-        """The fused entries of receive_axpby / receive_scaled / receive_scaled_add_ as [("cuda" | "cpu", names)]:
+        """The fused entries of receive_axpby / receive_scaled / receive_scaled_add_ / receive_add_ as [("cuda" |
+        "cpu", names)] (receive_add_ fuses the "cuda" group only):
         entries _receive would decode on the device (``_fusable``) whose tensor in every model of `models` is
         fp32, contiguous, 16-byte aligned, of the decoded shape, and with the others either on the staging device
         or on the CPU. models None (receive_scaled): grouped by where the payload, hence the decoded tensor,
@@ -537,7 +535,9 @@ def _apply_fused(channel: "_CodecChannel", c_params: QuantParameters, names: Lis
     dev = st.device
     stream = torch.cuda.current_stream(dev)
     lay, launch = channel._apply_payload(c_params, names, st)
-    shapes = [torch.Size(channel._apply_shape(c_params.params[n])) for n in names]
+    # the in-place device update (receive_add_, receive_scaled_add_) creates nothing
+    shapes = None if where == "cuda" and inplace else [torch.Size(channel._apply_shape(c_params.params[n]))
+                                                       for n in names]
     outs = None
     with torch.no_grad():
         if where == "cuda":

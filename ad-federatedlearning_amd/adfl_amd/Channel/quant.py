@@ -384,24 +384,6 @@ def _decode_host_dict(qlist: List[torch.Tensor], lay: ops.BucketLayout, st: _Dev
 
 
 @_serialized
-def _decode_add(c_params: QuantParameters, names: List[str], targets: List[Parameters]) -> None:
-    """Stage the qint8 payloads of `names` into an aligned bucket and accumulate them into every target."""
-    st = _staging()
-    dev = st.device
-    qs = [c_params.params[n].data for n in names]
-    for n, q in zip(names, qs):
-        if q.qscheme() != torch.per_tensor_affine or q.dtype != torch.qint8 or q.q_zero_point() != 0:
-            raise ValueError(f"SLQChannel: '{n}' is not a per-tensor qint8 payload with zero point 0")
-    lay = st.layout(tuple(int(q.numel()) for q in qs), align=ops.ALIGN_ELEMS)
-    q_dev = _stage_in([_int8_view(q) for q in qs], lay, st, "aq", torch.int8)
-    s_dev = torch.tensor([q.q_scale() for q in qs], dtype=torch.float32).to(dev, non_blocking=True)
-    with torch.no_grad():
-        ops.dequantize_add_batched(q_dev, s_dev, lay, [[t[n] for n in names] for t in targets])
-    # the next call's host gather rewrites the pinned staging this call's H2D reads from
-    torch.cuda.current_stream(dev).synchronize()
-
-
-@_serialized
 def _decode_mean(clients: List[List[torch.Tensor]], scales: List[List[float]], shapes: List[torch.Size],
                  packed: bool, apply=None) -> List[torch.Tensor]:
     """The fp32 mean over K clients of their decoded tensors, tensor by tensor, in torch's CPU summation
@@ -627,9 +609,10 @@ class SLQChannel(_CodecChannel):
     """Bi-directional symmetric linear quantization (quant.py:15-112) on the MI355X HIP codec:
     ``simulate_bandwidth`` counts self.bits for weights, 32 bits for biases, 32 bits per scale (quant.py:47-58).
 
-    ``receive_add_``: quantized tensors whose targets all live on the GPU are decoded once and accumulated
-    into every model by one launch (ops.dequantize_add_batched: the payload is read once, each model read and
-    written once, no decoded tensor is materialised). ``receive_mean``: tensors quantized in every update are
+    ``receive_add_``: quantized tensors whose targets all live on the GPU (``_apply_groups``' rule) are decoded
+    once and accumulated into every model by one launch (ops.dequantize_axpby_batched in place with alpha = beta
+    = 1: the payload is read once, each model read and written once, no decoded tensor is materialised; the
+    packed int4 channel unpacks in the same launch). ``receive_mean``: tensors quantized in every update are
     decoded and averaged by one launch of ops.dequantize_mean_batched."""
 
     def _receive(self, c_params: CompressedParameters) -> Tuple[Parameters, float]:
@@ -658,16 +641,6 @@ class SLQChannel(_CodecChannel):
             vals[i] = decoded[names[i]]
         rest()
         return dict(zip(names, vals)), time.perf_counter() - s_time
-
-    @staticmethod
-    def _add_fused(c_params: QuantParameters, targets: List[Parameters]) -> List[str]:
-        return [n for n, p in c_params.params.items()
-                if p.data.ndim > 1 and p.data.is_quantized and p.data.numel() > 0
-                and all(t[n].is_cuda and t[n].dtype == torch.float32 and t[n].is_contiguous()
-                        and t[n].data_ptr() % 16 == 0 for t in targets)]
-
-    def _decode_add(self, c_params: QuantParameters, names: List[str], targets: List[Parameters]) -> None:
-        _decode_add(c_params, names, targets)
 
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st: _DeviceStaging):
         """The qint8 payloads of `names` (``_fusable`` entries) in an aligned device bucket, and the fused decode

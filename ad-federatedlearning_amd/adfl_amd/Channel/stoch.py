@@ -734,22 +734,6 @@ def _decode_stoch_host(st, items, datas, numel: torch.Tensor, lptrs: np.ndarray,
     return outs
 
 
-@_serialized
-def _decode_add_stoch(items: List[Tuple[str, QuantParameter]], codec: str, bits: int,
-                      targets: List[List[torch.Tensor]]) -> None:
-    """Decode the payloads once into the device bucket and add it into every model (targets[k][j] += decode of
-    item j, fp32 adds: add_parameters_inpace's mul_(1).add_(d, alpha=1), model.py:337-347)."""
-    st = _staging()
-    lay, out_dev = _decode_stoch_bucket(st, items, codec, bits)
-    views = [out_dev[o:o + n].view(p.data.shape)
-             for o, n, (_, p) in zip(lay.offsets.tolist(), lay.sizes.tolist(), items)]
-    with torch.no_grad():
-        for model in targets:
-            torch._foreach_add_(model, views)
-    # the next call's staging rewrites the pinned buffers this call's H2D read and the bucket it decoded into
-    torch.cuda.current_stream(st.device).synchronize()
-
-
 def _decode_stoch_bucket(st, items: List[Tuple[str, QuantParameter]], codec: str, bits: int):
     """Both planes staged as one bucket on the device and decoded by one launch: (layout, fp32 bucket)."""
     dev = st.device
@@ -827,8 +811,9 @@ class _StochChannel(_CodecChannel):
     """Shared body of the three bi-directional stochastic channels: ``simulate_bandwidth`` counts self.bits + 1
     for weights and signs, 32 bits for biases, the norms (quant.py:173-184,313-324,459-470).
 
-    ``receive_add_``: encoded tensors whose targets are all fp32 tensors on the current device are decoded
-    once, into device memory, and added into every model there. ``receive_mean``: entries encoded in every
+    ``receive_add_``: encoded tensors whose targets are all on the current device (``_apply_groups``' rule) are
+    decoded and added into every model by one launch (stoch.dequantize_axpby_batched in place with alpha = beta
+    = 1: both planes read once, no decoded tensor written). ``receive_mean``: entries encoded in every
     update are decoded and averaged by one launch (each client's level and sign planes read once); empty
     tensors take the host route with the biases."""
 
@@ -861,20 +846,6 @@ class _StochChannel(_CodecChannel):
         for i, t in zip(pi, th.variable_data([datas[i] for i in pi])):
             vals[i] = t  # passthrough: q_param.data.data
         return dict(zip(names, vals)), time.perf_counter() - s_time
-
-    def _add_fused(self, c_params: QuantParameters, targets: List[Parameters]) -> List[str]:
-        fused = [n for n, p in c_params.params.items()
-                 if self._fusable(p) and all(t[n].is_cuda and t[n].dtype == torch.float32 for t in targets)]
-        if fused and targets:
-            dev = targets[0][fused[0]].device   # the staging's device (the current one) for the whole set
-            if dev.index != torch.cuda.current_device() or any(t[n].device != dev for t in targets for n in fused):
-                return []
-        return fused
-
-    def _decode_add(self, c_params: QuantParameters, names: List[str], targets: List[Parameters]) -> None:
-        if targets:
-            _decode_add_stoch([(n, c_params.params[n]) for n in names], self.CODEC, self.bits,
-                              [[t[n] for n in names] for t in targets])
 
     def _apply_payload(self, c_params: QuantParameters, names: List[str], st):
         """Both byte planes of `names` (``_fusable`` entries) in aligned device buckets, and the fused decode +
@@ -1272,8 +1243,8 @@ class _PackedStochChannel(_StochChannel):
     branch's 0-dim ``scale`` are the parent's. fp32 tensors only: another ndim > 1 dtype raises
     NotImplementedError. bits in [1, 8].
 
-    Fused here: ``receive_axpby``, ``receive_scaled`` and ``receive_scaled_add_`` (decode + axpby from the packed
-    planes, one launch). ``receive_add_``, ``receive_mean``, ``receive_mean_axpby``, ``receive_scaled_flush``,
+    Fused here: ``receive_axpby``, ``receive_scaled``, ``receive_scaled_add_`` and ``receive_add_`` (decode + axpby
+    from the packed planes, one launch). ``receive_mean``, ``receive_mean_axpby``, ``receive_scaled_flush``,
     ``FadasMoments.receive_flush``, ``send_delta`` and ``broadcast_delta_`` take ``_CodecChannel``'s non-fused
     route — ``_receive`` or ``diff_parameters`` + ``_send``, then the reference's torch statements — and return
     what the parent channel returns."""
@@ -1334,9 +1305,6 @@ class _PackedStochChannel(_StochChannel):
             self.CODEC, lv_dev, sb_dev, norms, lay, self.bits, bases, outs, alpha, beta, mins=mins)
 
     # -- not fused for packed planes: the parent's hooks read two byte planes of one byte per element ---------
-    def _add_fused(self, c_params: QuantParameters, targets: List[Parameters]) -> List[str]:
-        return []
-
     def _flush_groups(self, c_params: QuantParameters, models):
         return []
 
@@ -1352,21 +1320,7 @@ class _PackedStochChannel(_StochChannel):
     def _no_fused_form(self, *args, **kwargs):
         raise NotImplementedError(f"{self.__class__.__name__}: no fused form over packed planes")
 
-    _decode_add = _flush_payload = _mean_payloads = _mean_apply = _quantize_delta = _no_fused_form
-
-    def receive_add_(self, c_params: CompressedParameters, targets: List[Parameters]) -> float:
-        """``_receive(c_params)`` followed by ``add_parameters_inpace(t, decoded, 1, 1, False)`` for every target:
-        the parent's results by the non-fused route."""
-        assert isinstance(c_params, QuantParameters)
-        for t in targets:
-            assert set(t.keys()) == set(c_params.params.keys())  # add_parameters_inpace, model.py:340
-        s_time = time.perf_counter()
-        decoded, _ = self._receive(c_params)
-        with torch.no_grad():
-            for t in targets:
-                for n, d in decoded.items():
-                    t[n].mul_(1).add_(d.to(t[n].device), alpha=1)
-        return time.perf_counter() - s_time
+    _flush_payload = _mean_payloads = _mean_apply = _quantize_delta = _no_fused_form
 
     def send_delta(self, params_prev: Parameters, params_new: Parameters) -> Tuple[CompressedParameters, float]:
         """``_send(diff_parameters(params_prev, params_new))`` (Src/ADFL/model.py:350-358): the parent's payload,

@@ -510,8 +510,9 @@ def apply_tables(bases, outs, layout: BucketLayout, dev: torch.device):
     + axpby entries, after checking both sides against the layout (ValueError before anything is launched).
     An output may be its own base (in place); any other overlap between a base and an output is undefined."""
     o_ptrs, k = _apply_side(outs, layout, dev, "outs")
-    if bases is None:
-        return None, torch.from_numpy(np.ascontiguousarray(o_ptrs)).to(dev, non_blocking=True), k
+    if bases is None or bases is outs:   # SCALE, or in place: one side, checked once
+        tab = torch.from_numpy(np.ascontiguousarray(o_ptrs)).to(dev, non_blocking=True)
+        return (None if bases is None else tab), tab, k
     b_ptrs, kb = _apply_side(bases, layout, dev, "bases")
     if kb != k:
         raise ValueError(f"dequantize_axpby_batched: {kb} bases for {k} outputs")

@@ -155,15 +155,21 @@ def test_fedbuff_sequence(name, device):
 def test_scaled_add_with_factor_one_is_receive_add(name, device):
     """receive_add_ is the client's side (on_client_receive): a uni-directional channel's own receive_add_ takes
     no quantized payload (its clients receive through the identity channel, quant.py:115-137), so for USLQ / UQSGD
-    the comparison is with the same codec's bi-directional channel."""
+    the comparison is with the same codec's bi-directional channel. Both share one fused body, so both are also
+    compared with the reference's route computed on the host."""
     ch = CHANNELS[name]()
     c1, _, _ = payloads(name)
     a = [_model(60 + i, device) for i in range(2)]
     b = copy.deepcopy(a)
+    want = copy.deepcopy([{k: v.cpu() for k, v in m.items()} for m in a])
+    for m in want:
+        ref_add_(m, decode(ch, c1))
     ch.receive_scaled_add_(copy.deepcopy(c1), a, 1.0)
     CHANNELS[name[1:] if name.startswith("u") else name]().receive_add_(copy.deepcopy(c1), b)
-    for x, y in zip(a, b):
+    for x, y, w in zip(a, b, want):
         same_dict(x, y, (name, device))
+        same_dict(x, w, (name, device, "receive_scaled_add_ vs the host reference"))
+        same_dict(y, w, (name, device, "receive_add_ vs the host reference"))
 
 
 @pytest.mark.parametrize("name", ["slq8", "packed4", "rqsgd8"])

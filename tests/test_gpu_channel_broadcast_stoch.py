@@ -23,7 +23,6 @@ pytestmark = pytest.mark.gpu
 
 adfl_amd = pytest.importorskip("adfl_amd")
 from adfl_amd.Channel import CNATChannel, QSGDChannel, RQSGDChannel  # noqa: E402
-from adfl_amd.Channel import stoch as chs  # noqa: E402
 from adfl_amd.model import QuantParameters  # noqa: E402
 
 DEV = "cuda"
@@ -90,6 +89,17 @@ def _unfused(ch, hidden, new):
     return c
 
 
+def _no_coded_entry(ch):
+    """A receive_add_ for `ch` that fails when a coded payload entry reaches it: broadcast_delta_ hands it the
+    entries its fused launches did not take (the ndim <= 1 ones always), so a coded one came back in."""
+    real = ch.receive_add_
+
+    def receive_add_(c, targets):
+        assert not [n for n, p in c.params.items() if ch._fusable(p)], "the payload came back in"
+        return real(c, targets)
+    return receive_add_
+
+
 def _scalar_matches(row, v) -> bool:
     """A [kind, bits] row of the fixture (0 Python float, 1 the zero branch's 0-dim tensor, 2 an int) against a
     payload's scale / scale_2."""
@@ -113,9 +123,7 @@ def test_injected_uniforms_reproduce_every_step_of_the_reference(g, inputs, code
     hidden = _to(h0, h_dev, order)
     objects = {n: (id(t), t.data_ptr()) for n, t in hidden.items()}
 
-    def no_decode_add(*a, **k):
-        raise AssertionError("the payload came back in")
-    monkeypatch.setattr(chs, "_decode_add_stoch", no_decode_add)
+    monkeypatch.setattr(ch, "receive_add_", _no_coded_entry(ch))
     for k, new_np in enumerate(news, 1):
         pre = f"{run}__s{k}"
         new = _to(new_np, g_dev, new_order)
@@ -192,9 +200,7 @@ def test_a_fully_eligible_device_dict_never_takes_the_decode_and_add_route(input
     torch.manual_seed(77)
     want = _unfused(ch, ref, _clone(new))
 
-    def no_decode_add(*a, **k):
-        raise AssertionError("the payload came back in")
-    monkeypatch.setattr(chs, "_decode_add_stoch", no_decode_add)
+    monkeypatch.setattr(ch, "receive_add_", _no_coded_entry(ch))
     torch.manual_seed(77)
     got, _ = ch.broadcast_delta_(hidden, new)
     assert_same_payload(got, want)
@@ -225,12 +231,12 @@ def test_mixed_entries_fuse_what_the_rule_allows_and_route_the_rest(codec, monke
     want = _unfused(ch, ref, ref_new)
     objects = {n: id(t) for n, t in hidden.items()}
     routed = []
-    real = chs._decode_add_stoch
+    real = ch.receive_add_
 
-    def spy(items, *a, **k):
-        routed.extend(n for n, _ in items)
-        return real(items, *a, **k)
-    monkeypatch.setattr(chs, "_decode_add_stoch", spy)
+    def spy(c, targets):
+        routed.extend(n for n, p in c.params.items() if ch._fusable(p))
+        return real(c, targets)
+    monkeypatch.setattr(ch, "receive_add_", spy)
     torch.manual_seed(5)
     got, _ = ch.broadcast_delta_(hidden, new)
     assert_same_payload(got, want)

@@ -181,10 +181,12 @@ def test_channel_surface(name):
     for bits in range(1, 9):
         assert cls(bits).levels == 2 ** bits - 1
     # the fused hooks that would read two whole byte planes decline
-    assert ch._add_fused(None, []) == [] and ch._flush_groups(None, []) == []
+    assert ch._flush_groups(None, []) == []
     assert ch._mean_host_updates([], []) is None and ch._mean_host_classify([], []) is None
     assert ch._mean_fused_names([], ["w"]) == []
-    for hook in ("_decode_add", "_flush_payload", "_mean_payloads", "_mean_apply", "_quantize_delta"):
+    # receive_add_ is the shared body: the fused decode + axpby from the packed planes, in place with (1, 1)
+    assert cls.receive_add_ is _CodecChannel.receive_add_
+    for hook in ("_flush_payload", "_mean_payloads", "_mean_apply", "_quantize_delta"):
         with pytest.raises(NotImplementedError):
             getattr(ch, hook)()
     uni = name.startswith("U")

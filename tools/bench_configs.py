@@ -38,6 +38,10 @@ bench.py measures the headline (C2). This tool measures the rest on the same cod
             one process, at 8 and 4 bits, on the C3-shaped dict and one 2^26-element tensor: device-resident
             quantize, decode and decode + axpby (HIP events, Infinity Cache flushed, medians of --steps calls) and
             the host-to-host encode + decode round trip (wall); a parity flag per leg
+  receive_add  receive_add_ into a device-resident model from a CPU payload, per channel (SLQ 8, PackedSLQ 4, QSGD 8,
+            RQSGD 8, CNAT 8, PackedQSGD 8; wall), and ops.dequantize_add_batched alone into K = 1 and 4 models (HIP
+            events), on the C3-shaped dict and one 2^26-element tensor; public calls only, so a worktree of the
+            parent commit runs the same file and --baseline <its JSON line> judges every leg against it
 
     python tools/bench_configs.py --mode c3
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_configs.py --mode exchange
@@ -2139,6 +2143,134 @@ def mode_packed_stoch(args, world, rank, dev):
     return line
 
 
+def _receive_add_leg(sizes, args, dev, junk, repeats=3):
+    """One layout of the receive_add mode. Whole call (wall, Infinity Cache read-flushed before every call):
+    ch.receive_add_(c, [model]) with a device-resident model and the CPU payload a client sent, per channel.
+    Kernel alone (HIP events, flushed likewise): ops.dequantize_add_batched into K = 1 and K = 4 device models.
+    Every figure is `repeats` medians of args.steps calls, all listed. "digest": sha256 over the model after one
+    call from a fixed start, so two commits' runs can be compared bit for bit. Only public calls."""
+    import hashlib
+
+    from adfl_amd import ops
+    from adfl_amd.Channel import (CNATChannel, PackedQSGDChannel, PackedSLQChannel, QSGDChannel, RQSGDChannel,
+                                  SLQChannel)
+    gen = torch.Generator().manual_seed(0)
+    update, start = {}, {}
+    for i, n in enumerate(sizes):
+        for name, shape in ((f"layer{i:03d}.weight", (1, n)), (f"layer{i:03d}.bias", (64,))):
+            update[name] = torch.randn(shape, generator=gen) * 1e-2
+            start[name] = torch.randn(shape, generator=gen)
+
+    def digest(tensors):
+        h = hashlib.sha256()
+        for t in tensors:
+            h.update(t.detach().cpu().contiguous().numpy().tobytes())
+        return h.hexdigest()[:16]
+
+    def medians(fn, sync_wall):
+        out = []
+        for _ in range(repeats):
+            if sync_wall:
+                ms = []
+                for _ in range(args.steps):
+                    junk.amax()   # read-flush of the Infinity Cache
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    ms.append((time.perf_counter() - t0) * 1e3)
+            else:
+                _, evs = timed(fn, args.steps, args.warmup, 1, 2)
+                ms = [e[0].elapsed_time(e[1]) for e in evs]
+            out.append(round(_median(ms), 4))
+        return out
+
+    res = {"tensors": len(sizes), "elements": int(sum(sizes))}
+    channels = {"slq8": SLQChannel(8), "packed_slq4": PackedSLQChannel(4), "qsgd8": QSGDChannel(8),
+                "rqsgd8": RQSGDChannel(8), "cnat8": CNATChannel(8), "packed_qsgd8": PackedQSGDChannel(8)}
+    for key, ch in channels.items():
+        torch.manual_seed(1)   # the stochastic encodes draw their Philox seed from torch's CPU generator
+        c = ch.on_client_send(update)[0]
+        model = {k: v.to(dev) for k, v in start.items()}
+        ch.receive_add_(c, [model])
+        leg = {"digest": digest(model.values())}
+        for _ in range(args.warmup):
+            ch.receive_add_(c, [model])
+        leg["ms_repeats"] = medians(lambda: ch.receive_add_(c, [model]), True)
+        leg["ms"] = _median(leg["ms_repeats"])
+        res[f"receive_add_{key}"] = leg
+        del c, model
+
+    lay = ops.BucketLayout(list(sizes))
+    x = torch.cat([update[k].reshape(-1) for k in update if update[k].ndim > 1]).to(dev)
+    flat = torch.zeros(lay.total, device=dev)
+    for o, n, s in zip(lay.offsets.tolist(), lay.sizes.tolist(), torch.split(x, list(sizes))):
+        flat[o:o + n] = s
+    q, scales = ops.encode_batched(flat, lay, 8)
+    del x, flat
+    for k in (1, 4):
+        targets = [[start[n].reshape(-1).to(dev) for n in start if start[n].ndim > 1] for _ in range(k)]
+        ops.dequantize_add_batched(q, scales, lay, targets)
+        leg = {"digest": digest(t for m in targets for t in m)}
+
+        def step(ev):
+            junk.amax()
+            if ev is not None:
+                ev[0].record()
+            ops.dequantize_add_batched(q, scales, lay, targets)
+            if ev is not None:
+                ev[1].record()
+        leg["ms_repeats"] = medians(step, False)
+        leg["ms"] = _median(leg["ms_repeats"])
+        res[f"kernel_alone_k{k}"] = leg
+        del targets
+    return res
+
+
+def mode_receive_add(args, world, rank, dev):
+    """receive_add_ (decode a payload and add it into device-resident models in place) on the C3-shaped dict and on
+    one 2^26-element tensor: the whole call per channel (wall) and ops.dequantize_add_batched alone (HIP events), see
+    _receive_add_leg. The mode uses only public calls, so the same file measures any commit: run it from a git
+    worktree of the parent commit with its own build, keep that run's JSON line, and give it to the run on this
+    commit as --baseline. That run then judges every leg as the broadcast mode judges its own (this commit's median
+    of repeats not above the parent's worst repeat: the margin is the parent's own spread), compares the digests,
+    and writes both commits' figures to profiles/receive_add/receive_add.json."""
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    import recipes
+    junk = torch.zeros(128 << 20, dtype=torch.float32, device=dev)
+    legs = {"c3_dict": _receive_add_leg(list(recipes.bucket_sizes("equal")), args, dev, junk),
+            "one_tensor_2p26": _receive_add_leg([args.elems or 1 << 26], args, dev, junk)}
+    line = {"mode": "receive_add", "metric": "SLQChannel(8).receive_add_ into one device-resident model, CPU payload, "
+            "C3-shaped dict, Infinity Cache flushed", "unit": "ms", "value": legs["c3_dict"]["receive_add_slq8"]["ms"],
+            "steps": args.steps, "repeats": 3, **legs}
+    if not args.baseline:
+        return line
+    with open(args.baseline) as f:
+        parent = json.loads([ln for ln in f.read().splitlines() if ln.startswith("{")][-1])
+    verdicts = {}
+    for layout, new in legs.items():
+        for key, leg in new.items():
+            if not isinstance(leg, dict):
+                continue
+            old = parent[layout][key]
+            verdicts[f"{layout}.{key}"] = {
+                "parent_ms": old["ms"], "parent_ms_repeats": old["ms_repeats"], "ms": leg["ms"],
+                "ms_repeats": leg["ms_repeats"], "over_parent": round(leg["ms"] / old["ms"], 4),
+                "not_above_parent_worst_repeat": bool(leg["ms"] <= max(old["ms_repeats"])),
+                "same_bits_as_parent": leg["digest"] == old["digest"]}
+    doc = {"mode": "receive_add", "unit": "ms", "steps": args.steps, "repeats": 3,
+           "parity": all(v["same_bits_as_parent"] for v in verdicts.values()),
+           "legs_not_above_parent_worst_repeat": f"{sum(v['not_above_parent_worst_repeat'] for v in verdicts.values())} "
+                                                 f"of {len(verdicts)}", "legs": verdicts}
+    out_dir = os.path.join(REPO, "profiles", "receive_add")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "receive_add.json"), "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    return {**line, "parity": doc["parity"],
+            "legs_not_above_parent_worst_repeat": doc["legs_not_above_parent_worst_repeat"]}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--serial", action="store_true", help="exchange: no side stream (quantize + all-gather in order)")
@@ -2147,7 +2279,7 @@ def main():
                    help="exchange: one flat update per rank, or a C3 state dict with per-tensor scales")
     p.add_argument("--mode", choices=["c3", "c5_int4", "exchange", "pcie", "channel", "channel_stoch", "stoch",
                                       "delta", "delta_stoch", "apply", "flush", "broadcast", "broadcast_stoch",
-                                      "sync_delta", "receive_flush", "packed_stoch"],
+                                      "sync_delta", "receive_flush", "packed_stoch", "receive_add"],
                    required=True)
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -2156,6 +2288,7 @@ def main():
     p.add_argument("--packed", action="store_true")
     p.add_argument("--chunks", type=int, default=1)
     p.add_argument("--no-cpu", action="store_true", help="stoch: skip the host reference timing")
+    p.add_argument("--baseline", default="", help="receive_add: the JSON line of this mode run on the parent commit")
     args = p.parse_args()
     rc = maybe_launch(args.gpus, os.path.abspath(__file__), sys.argv[1:])
     if rc is not None:
@@ -2168,7 +2301,7 @@ def main():
             "delta": mode_delta, "delta_stoch": mode_delta_stoch, "apply": mode_apply,
             "flush": mode_flush, "broadcast": mode_broadcast, "broadcast_stoch": mode_broadcast_stoch,
             "sync_delta": mode_sync_delta, "receive_flush": mode_receive_flush,
-            "packed_stoch": mode_packed_stoch}[args.mode](
+            "packed_stoch": mode_packed_stoch, "receive_add": mode_receive_add}[args.mode](
         args, world, rank, dev)
     if rank == 0:
         print(json.dumps(line), flush=True)
